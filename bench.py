@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: HR Mpixels/s of the LarvaNet x4 multi-exit TRAINING step on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--extras]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full [--extras]]
 
 N > 1 works both ways: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py
 --gpus N ...` (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment), or as a plain
@@ -14,17 +14,23 @@ gradient all-reduce over RCCL when N > 1, AdamW -- i.e. train_step_larva (models
 of the reference) at the BASELINE configuration: 16 x 3 x 48 x 48 fp32 patches per GPU -> 16 x 3 x
 192 x 192, `--num_modules=4 --num_blocks=4,4,4,4`, 48 channels (the only channel count the
 reference can express).  value = N * 16 * 192 * 192 / t_step (pixels counted once).
-The K-step loop is timed --rounds times (barrier + synchronize on both sides of each); value and
-ms_per_step are the MEDIAN round, min / max are reported beside it.  The loop has the reference's
-semantics: every step is handed fresh device tensors (train_larva.py:123-128) and returns loss.item()
-(models/LarvaNet.py:139).
+Exactly K steps are timed, as --rounds consecutive rounds of about K / rounds steps each (barrier +
+synchronize on both sides of each); value and ms_per_step are the MEDIAN round's time per step, min / max
+are reported beside it.  Before them run the W warm-up steps and a fixed 100 settle steps (the clock ramp),
+so the state the timed steps start from depends on W alone.  The loop has the reference's semantics: every
+step is handed fresh device tensors (train_larva.py:123-128) and returns loss.item() (models/LarvaNet.py:139).
+
+A plain run does only that: set up, warm up, time the K steps, write --dump-outputs, print the line.
+--dump-outputs DIR writes what the last timed step computed, as a caller of train_step_larva holds it:
+loss.npy (float64), param.<name>.npy and grad.<name>.npy (float32) for every parameter (~7 MB).  The inputs
+and the weights are seeded, so two builds run with the same arguments can be compared array for array.
 
 OUTPUT.  stdout carries exactly ONE line: a COMPACT JSON object (<= 4 KB, no prose fields; `compact_line`
-below names every key it keeps).  The FULL record -- every block with its method notes -- goes to
-`bench_full.json` (in $LARVA_BENCH_FULL, else gpurun_out/ when it exists, else beside this file) and, as one
-line prefixed `bench_full: `, to stderr.
+below names every key it keeps).  With --full, the FULL record -- every block with its method notes -- goes
+to `bench_full.json` (in $LARVA_BENCH_FULL, else where full_record_path() puts it) and, as one line
+prefixed `bench_full: `, to stderr.
 
-Blocks of the default run (all in the compact line):
+Blocks of a --full run (all in the compact line):
   roofline            fp32-MFMA roofline of the dominant kernel (fused conv3x3+ReLU, 48->48, 16x48x48) the way
                       the step runs it: two concurrent half-batch strip-tile launches per layer; avg_ms = replay
                       of a captured 40-link graph / 40 (the step's own chain length), settled like the headline,
@@ -37,10 +43,10 @@ Blocks of the default run (all in the compact line):
   infer_full_image    V1 on one 3 x 339 x 510 image (BASELINE config 5 at N = 1) + its dominant layer
   cpu_baseline        the same training step in the torch CPU restatement (oracle/, kind "port") on the host
                       cores of this box, bounded sample; configs[0] (EDSR-baseline CPU step) beside it
-  rccl_ranks, allreduce_exposed_us, dp_schedule, ms_per_step_per_rank     N > 1 only
---extras adds (full record only): the whole-batch single chain, 32 / 64 channels, V2 full-image inference, the
-data-parallel schedules on one GPU with and without a one-rank RCCL communicator, the async / resident loop, the
-chains' in-step marker timing, the sustained clock.
+  rccl_ranks, allreduce_exposed_us, dp_schedule, ms_per_step_per_rank     N > 1 only (plain runs too)
+--extras (implies --full) adds (full record only): the whole-batch single chain, 32 / 64 channels, V2 full-image
+inference, the data-parallel schedules on one GPU with and without a one-rank RCCL communicator, the async / resident
+loop, the chains' in-step marker timing, the sustained clock.
 """
 import argparse
 import json
@@ -64,6 +70,8 @@ FLAGS = ["--num_modules=4", "--num_blocks=4,4,4,4"]
 HR_PIX_PER_BATCH = BATCH * (PATCH * SCALE) ** 2          # 589 824
 FP32_MFMA_PEAK_TFLOPS = 157.3                            # MI355X_MICROARCH.md: Peak FP32 (matrix)
 FULL_IMAGE = (3, 339, 510)                               # DIV2K-val-like LR image
+SETTLE_BLOCKS = 10                                       # untimed blocks of 10 steps between warm-up and the timed steps
+DUMP_MAX_BYTES = 64 << 20                                # --dump-outputs writes at most this much
 # HBM-side bytes per launch, the MFMA-busy fraction and the lone-launch duration come from the committed rocprofv3 passes
 # (counters cannot be collected by this run itself); they are READ from the CSVs under profiles/ at run time -- newest
 # round first -- and the file used is named in the record: a kernel change that is not followed by new passes shows as a
@@ -891,13 +899,20 @@ def guarded(line, key, fn):
 guarded.fault = None
 
 
-def timed_rounds(model, args, val, x, truth, steps, rounds, dist_on):
-    """`rounds` x (barrier + sync, `steps` steps, barrier + sync) -> seconds per round, max over ranks."""
+def round_sizes(steps, rounds):
+    """`steps` timed steps as min(rounds, steps) consecutive rounds whose sizes differ by at most one step."""
+    n = max(1, min(rounds, steps))
+    return [steps // n + (1 if i < steps % n else 0) for i in range(n)]
+
+
+def timed_rounds(model, args, val, x, truth, sizes, dist_on):
+    """One round per entry of `sizes` (barrier + sync, that many steps, barrier + sync) -> seconds per round, max over
+    ranks."""
     import torch
     import torch.distributed as td
     secs = []
     loss = None
-    for _ in range(rounds):
+    for steps in sizes:
         barrier_sync(dist_on)
         t0 = time.perf_counter()
         for _ in range(steps):
@@ -917,6 +932,26 @@ def timed_rounds(model, args, val, x, truth, steps, rounds, dist_on):
         secs = [float(v) for v in t.cpu()]
     timed_rounds.per_rank = per_rank
     return secs, loss
+
+
+def dump_outputs(model, loss, out_dir):
+    """--dump-outputs: what the last timed step computed, as a caller of train_step_larva holds it -- the loss it returned
+    (loss.npy, float64) and every parameter after the step's AdamW update with the gradient the step computed for it
+    (param.<name>.npy / grad.<name>.npy, float32): ~7 MB at the headline configuration."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    arrays = {"loss": np.asarray(float(loss), dtype=np.float64)}
+    for name, p in model.model.named_parameters():
+        arrays["param." + name] = p.detach().float().cpu().numpy()
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad.detach().float().cpu().numpy()
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes of outputs (> %d)" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def dp_probe_child(a, emit):
@@ -957,7 +992,7 @@ def dp_probe_child(a, emit):
             m.train_step_larva(args, val, x, truth)
         if hasattr(m, "allreduce_events"):
             m.allreduce_events.clear()
-        secs, _ = timed_rounds(m, args, val, x, truth, a.steps, 3, False)
+        secs, _ = timed_rounds(m, args, val, x, truth, [a.steps] * 3, False)
         ms = float(np.median([s / a.steps * 1e3 for s in secs]))
         res = {"ms_per_step": ms, "schedule_ran": m.dp_schedule.get("choice"), "late_graph": getattr(m, "_graph_late", None) is not None,
                "split_at_float": getattr(m, "_early_lo", None)}
@@ -1021,15 +1056,17 @@ def dry_run(a, rank, world, emit):
         td.barrier()
         td.all_reduce(t, op=td.ReduceOp.MAX)
     if rank == 0:
-        full = headline_record(a, world, ms_rounds=[1.0 + 0.001 * i for i in range(max(1, a.rounds))], settle_steps=20,
+        n_rounds = len(round_sizes(a.steps, a.rounds))
+        full = headline_record(a, world, ms_rounds=[1.0 + 0.001 * i for i in range(n_rounds)], settle_steps=20,
                                final_loss=0.0, ref_semantics=True, hip_graph=True, dual_chain=True, fell_back=None, resident=False)
-        full.update({"dry_run": True, "max_rank_plus_1": float(t.item()), "backend": td.get_backend() if world > 1 else None,
-                     "roofline": {"bound": "mfma", "achieved": 0.0, "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": 0.0,
-                                  "frac_min": 0.0, "frac_max": 0.0, "sets": 7, "traffic": None, "avg_ms": 0.0,
-                                  "kernel": "dry run: no kernel was launched", "flop_per_layer": conv_flop(CH)}})
+        full.update({"dry_run": True, "max_rank_plus_1": float(t.item()), "backend": td.get_backend() if world > 1 else None})
+        if a.full:
+            full["roofline"] = {"bound": "mfma", "achieved": 0.0, "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": 0.0,
+                                "frac_min": 0.0, "frac_max": 0.0, "sets": 7, "traffic": None, "avg_ms": 0.0,
+                                "kernel": "dry run: no kernel was launched", "flop_per_layer": conv_flop(CH)}
         if world > 1:
             full.update({"rccl_ranks": 0, "dist_backend": td.get_backend(),
-                         "allreduce_exposed_us": {"median": 0.0, "min": 0.0, "max": 0.0, "steps": a.steps * a.rounds, "overlap": False},
+                         "allreduce_exposed_us": {"median": 0.0, "min": 0.0, "max": 0.0, "steps": a.steps, "overlap": False},
                          "dp_schedule": {"choice": "flat", "allreduce_isolated_us": 0.0, "bucket_bytes": 3330816, "ranks": world,
                                          "rule": "dry run"},
                          "ms_per_step_per_rank": {"min": 1.0, "max": 1.0, "ranks": [1.0] * world}})
@@ -1040,7 +1077,8 @@ def dry_run(a, rank, world, emit):
 
 
 def headline_record(a, world, ms_rounds, settle_steps, final_loss, ref_semantics, hip_graph, dual_chain, fell_back, resident):
-    """The contract's keys of the record from the timed rounds (ms per step of every round, in the order they ran)."""
+    """The contract's keys of the record from the timed rounds (ms per step of every round, in the order they ran; the
+    rounds split the a.steps timed steps as round_sizes does)."""
     import numpy as np
     per_step = sorted(ms_rounds)
     ms_per_step = float(np.median(per_step))
@@ -1059,7 +1097,8 @@ def headline_record(a, world, ms_rounds, settle_steps, final_loss, ref_semantics
                               "fresh device tensors handed to train_step_larva every step (copied into the captured step's inputs)"),
                    "loss_sync_per_step": bool(ref_semantics), "hip_graph": bool(hip_graph), "dual_chain": bool(dual_chain),
                    "hip_graph_fell_back": fell_back, "final_loss": final_loss},
-        "rounds": {"n": len(ms_rounds), "steps_each": a.steps, "value_is": "median round (max over ranks of each round's wall time)"},
+        "rounds": {"n": len(ms_rounds), "steps_each": round_sizes(a.steps, len(ms_rounds)),
+                   "value_is": "median round (max over ranks of each round's wall time)"},
     }
 
 
@@ -1068,12 +1107,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--rounds", type=int, default=5, help="the --steps loop is timed this many times; value = median")
+    ap.add_argument("--rounds", type=int, default=5,
+                    help="the --steps timed steps run as this many consecutive rounds; value = the median round")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's loss, parameters and gradients to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline, step, infer, roofline_wgrad, infer_full_image, "
+                         "cpu_baseline and the full record (bench_full.json)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--extras", action="store_true",
-                    help="the extra single-GPU measurements (other widths, V2 inference, one-GPU data-parallel rehearsals, ...): "
-                         "full record only, + ~40 s")
-    ap.add_argument("--no-extras", action="store_true", help="headline + `roofline` only (rocprofv3 --kernel-trace runs)")
+                    help="implies --full; the extra single-GPU measurements (other widths, V2 inference, one-GPU data-parallel "
+                         "rehearsals, ...): full record only, + ~40 s")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="implies --full; headline + `roofline` only (rocprofv3 --kernel-trace runs)")
     ap.add_argument("--roofline-only", action="store_true",
                     help="only time the dominant kernel (short run for rocprofv3 --pmc passes)")
     ap.add_argument("--wgrad-only", action="store_true",
@@ -1085,6 +1131,9 @@ def main():
                     help="headline loop without the reference's per-step loss.item() and with the batch already in the "
                          "captured step's input buffers (round 2's headline; now the `value_async_resident` extra)")
     a = ap.parse_args()
+    a.full = a.full or a.extras or a.no_extras
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher BEFORE anything touches the GPU
@@ -1101,8 +1150,11 @@ def main():
         os.write(json_fd, (json.dumps(obj) + "\n").encode())
 
     def emit(full):
-        """Full record -> bench_full.json + stderr; compact line -> stdout (the only stdout line)."""
+        """--full: full record -> bench_full.json + stderr.  Compact line -> stdout (the only stdout line)."""
         full["bench_wall_s"] = time.perf_counter() - t_start
+        if not a.full:
+            os.write(json_fd, (compact_line(full) + "\n").encode())
+            return
         path = full_record_path()
         try:
             with open(path, "w") as f:
@@ -1182,31 +1234,33 @@ def main():
     section("prepare_and_warmup", t0)
     # Settle: the W warm-up steps above are ~10 ms of GPU work behind the idle time of start-up, and the chip needs longer
     # than that under load to reach the clocks it then holds -- the first 10 steps after ANY idle gap run ~5 % slow
-    # (tools/step_ramp.py: 1.72 ms, then 1.64 flat; again after a 0.5 s pause).  So untimed steps go on in blocks of 10
-    # until two consecutive blocks agree within 0.5 % (at most 10 blocks); every timed round then starts on a warm chip.
+    # (tools/step_ramp.py: 1.72 ms, then 1.64 flat; again after a 0.5 s pause).  So 10 blocks of 10 untimed steps run
+    # (~0.17 s) and every timed round starts on a warm chip.  Always all 10 -- the weights the timed steps start from
+    # (--dump-outputs) must not depend on the clock -- and settle_steps reports where two consecutive blocks first
+    # agreed within 0.5 % (rank 0's view; 100 if they never did).
     t0 = time.perf_counter()
-    settle_steps, prev = 0, None
-    for _ in range(10):
+    settle_steps, prev = None, None
+    for blk in range(SETTLE_BLOCKS):
         barrier_sync(world > 1)
         t1 = time.perf_counter()
         for _ in range(10):
             model.train_step_larva(args, val, x, truth)
         barrier_sync(world > 1)
         cur = time.perf_counter() - t1
-        settle_steps += 10
-        ok = prev is not None and abs(cur - prev) <= 0.005 * prev
-        if world > 1:   # every rank must take the same decision
-            flag = torch.tensor([1.0 if ok else 0.0], device=dev)
-            td.all_reduce(flag, op=td.ReduceOp.MIN)
-            ok = bool(flag.item() > 0.5)
+        if settle_steps is None and prev is not None and abs(cur - prev) <= 0.005 * prev:
+            settle_steps = 10 * (blk + 1)
         prev = cur
-        if ok:
-            break
+    if settle_steps is None:
+        settle_steps = 10 * SETTLE_BLOCKS
     if hasattr(model, "allreduce_events"):
         model.allreduce_events.clear()
-    rounds = max(1, a.rounds)
-    secs, loss = timed_rounds(model, args, val, x, truth, a.steps, rounds, world > 1)
+    sizes = round_sizes(a.steps, a.rounds)
+    secs, loss = timed_rounds(model, args, val, x, truth, sizes, world > 1)
     section("settle_and_timed_rounds", t0)
+    if a.dump_outputs and rank == 0:
+        t0 = time.perf_counter()
+        dump_outputs(model, loss, a.dump_outputs)
+        section("dump_outputs", t0)
     exposed = None
     if world > 1 and getattr(model, "allreduce_events", None):
         torch.cuda.synchronize()
@@ -1223,10 +1277,11 @@ def main():
             td.destroy_process_group()
         return
 
-    line = headline_record(a, world, [s / a.steps * 1e3 for s in secs], settle_steps, float(loss), ref_semantics,
+    line = headline_record(a, world, [s / n * 1e3 for s, n in zip(secs, sizes)], settle_steps, float(loss), ref_semantics,
                            model.use_hip_graph, model.dual_chain, model.hip_graph_fell_back, resident=bufs is not None and not ref_semantics)
     ms_per_step = line["ms_per_step"]
     line["sections_s"] = sections
+    line["settle_steps_run"] = 10 * SETTLE_BLOCKS
     if world > 1:
         line["rccl_ranks"] = td.get_world_size() if td.get_backend() == "nccl" else 0
         line["dist_backend"] = td.get_backend()
@@ -1234,16 +1289,18 @@ def main():
         line["dp_schedule"] = model.dp_schedule   # isolated all-reduce time measured at prepare() and the schedule it chose
         if getattr(timed_rounds, "per_rank", None):
             # every rank's own ms_per_step (median round): a straggler or an exposed collective shows here
-            per = [float(np.median([s / a.steps * 1e3 for s in r])) for r in timed_rounds.per_rank]
+            per = [float(np.median([s / n * 1e3 for s, n in zip(r, sizes)])) for r in timed_rounds.per_rank]
             line["ms_per_step_per_rank"] = {"min": min(per), "max": max(per), "ranks": per}
 
+    # Everything below is --full only: a plain run ends with its headline (and --dump-outputs, written above).
     # the whole step against the fp32 matrix peak: the only fraction tied to the driver-timed number.  SURVEY 8(d):
     # forward 40 C->C convs + head, backward dgrad + wgrad per C->C conv + the head's wgrad (elementwise work excluded)
-    flop_step = (2 * sum(BLOCKS) + 2 * len(BLOCKS)) * 3 * conv_flop(CH) + 2 * (2 * 9 * 3 * CH * BATCH * PATCH * PATCH)
-    line["step"] = {"flop_per_step": flop_step, "achieved": flop_step / (ms_per_step * 1e-3) / 1e12, "unit": "TFLOP/s",
-                    "peak": FP32_MFMA_PEAK_TFLOPS, "frac_of_peak": flop_step / (ms_per_step * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS}
-    extras = world == 1 and a.extras and not a.no_extras
-    basic = world == 1 and not a.no_extras
+    if a.full:
+        flop_step = (2 * sum(BLOCKS) + 2 * len(BLOCKS)) * 3 * conv_flop(CH) + 2 * (2 * 9 * 3 * CH * BATCH * PATCH * PATCH)
+        line["step"] = {"flop_per_step": flop_step, "achieved": flop_step / (ms_per_step * 1e-3) / 1e12, "unit": "TFLOP/s",
+                        "peak": FP32_MFMA_PEAK_TFLOPS, "frac_of_peak": flop_step / (ms_per_step * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFLOPS}
+    extras = a.full and world == 1 and a.extras and not a.no_extras
+    basic = a.full and world == 1 and not a.no_extras
 
     # The clock the chip sustains under this load (the guide's 157.3 TFLOP/s is 2.4 GHz): one napping wave on a side stream
     # counts shader cycles against the 100 MHz wall clock while 40 more steps run (measurement library; untimed).
@@ -1269,12 +1326,13 @@ def main():
                 line["step"]["sustained_clock_error"] = "%s: %s" % (type(e).__name__, e)
 
     # the REQUIRED block first (`roofline`): a fault inside a later block then cannot cost the line its roofline
-    t0 = time.perf_counter()
-    dual = roofline_block(dev, dual=True, extras=extras) if model.dual_chain else None
-    # the dominant kernel as the step runs it: the pair of strip-tile launches when the layer chain
-    # runs as two half-batch chains, else the whole-batch launch
-    line["roofline"] = dual if dual is not None else roofline_block(dev, dual=False, extras=extras)
-    section("roofline", t0)
+    if a.full:
+        t0 = time.perf_counter()
+        dual = roofline_block(dev, dual=True, extras=extras) if model.dual_chain else None
+        # the dominant kernel as the step runs it: the pair of strip-tile launches when the layer chain
+        # runs as two half-batch chains, else the whole-batch launch
+        line["roofline"] = dual if dual is not None else roofline_block(dev, dual=False, extras=extras)
+        section("roofline", t0)
     if basic:
         t0 = time.perf_counter()
         with torch.no_grad():
@@ -1312,7 +1370,7 @@ def main():
         t0 = time.perf_counter()
         guarded(line, "roofline_wgrad", wgrad_in_the_step)
         section("roofline_wgrad", t0)
-    elif world > 1:
+    elif a.full and world > 1:
         line["roofline_wgrad"] = wgrad_block(dev)
 
     if extras:
@@ -1324,7 +1382,7 @@ def main():
             def async_resident():
                 model.sync_loss = False
                 try:
-                    secs2, _ = timed_rounds(model, args, val, bufs[0], bufs[1], a.steps, min(rounds, 3), False)
+                    secs2, _ = timed_rounds(model, args, val, bufs[0], bufs[1], [a.steps] * min(max(1, a.rounds), 3), False)
                 finally:
                     model.sync_loss = True
                 ms2 = float(np.median([s / a.steps * 1e3 for s in secs2]))
@@ -1358,7 +1416,7 @@ def main():
             mw.sync_loss = ref_semantics
             for _ in range(max(a.warmup, 1)):
                 mw.train_step_larva(args, val, x_fresh, truth_fresh)
-            secs_w, _ = timed_rounds(mw, args, val, x_fresh, truth_fresh, a.steps, min(rounds, 3), False)
+            secs_w, _ = timed_rounds(mw, args, val, x_fresh, truth_fresh, [a.steps] * min(max(1, a.rounds), 3), False)
             ms_w = float(np.median([s / a.steps * 1e3 for s in secs_w]))
             with torch.no_grad():
                 for _ in range(5):
@@ -1392,7 +1450,7 @@ def main():
         t0 = time.perf_counter()
         guarded(line, "infer_full_image", lambda: full_image_block(dev, extras=extras))
         section("infer_full_image", t0)
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         t0 = time.perf_counter()
         line["cpu_baseline"] = cpu_baseline()
         sections["cpu_baseline"] = round(time.perf_counter() - t0, 3)

@@ -113,14 +113,19 @@ def test_compact_line_refuses_to_grow_past_the_limit():
         B.COMPACT_MAX_BYTES = old
 
 
+def _dry_env(tmp_path):
+    env = dict(os.environ, LARVA_BENCH_DRY="1", OMP_NUM_THREADS="1", LARVA_BENCH_FULL=str(tmp_path))
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
+        env.pop(k, None)
+    return env
+
+
 @pytest.mark.timeout(300)
 @pytest.mark.parametrize("n", [1, 8])
 def test_dry_run_emits_the_compact_line_and_the_full_record(n, tmp_path):
     """The whole emit path (launcher -> rank 0 -> stdout) at N = 1 and N = 8 with the N > 1 fields present."""
-    env = dict(os.environ, LARVA_BENCH_DRY="1", OMP_NUM_THREADS="1", LARVA_BENCH_FULL=str(tmp_path))
-    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
-        env.pop(k, None)
-    r = subprocess.run([sys.executable, BENCH, "--gpus", str(n), "--steps", "20", "--warmup", "5"], env=env,
+    env = _dry_env(tmp_path)
+    r = subprocess.run([sys.executable, BENCH, "--gpus", str(n), "--steps", "20", "--warmup", "5", "--full"], env=env,
                        capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -136,3 +141,67 @@ def test_dry_run_emits_the_compact_line_and_the_full_record(n, tmp_path):
     full = json.load(open(os.path.join(str(tmp_path), "bench_full.json")))
     assert full["n_gpus"] == n and "ms_per_step_rounds" in full
     assert any(l.startswith("bench_full: {") for l in r.stderr.splitlines())
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("n", [1, 2])
+def test_plain_dry_run_is_the_headline_alone(n, tmp_path):
+    """Without --full the line carries the contract's keys (and the N > 1 fields of the timed steps) but none of the
+    blocks that take runs of their own, and no full record is written."""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", str(n), "--steps", "7", "--warmup", "2"], env=_dry_env(tmp_path),
+                       capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    for k in CONTRACT:
+        assert k in line, k
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["n_gpus"] == n
+    for k in ("roofline", "roofline_wgrad", "step", "infer", "infer_full_image", "cpu_baseline", "full_record"):
+        assert k not in line, k
+    if n > 1:
+        assert len(line["ms_per_step_per_rank"]["ranks"]) == n and line["allreduce_exposed_us"]["steps"] == 7
+    assert os.listdir(str(tmp_path)) == []
+    assert not any(l.startswith("bench_full: ") for l in r.stderr.splitlines())
+
+
+@pytest.mark.parametrize("steps,rounds", [(1, 5), (3, 5), (7, 5), (20, 5), (50, 5), (10, 1), (4, 0)])
+def test_timed_rounds_split_exactly_the_given_steps(steps, rounds):
+    sizes = _bench().round_sizes(steps, rounds)
+    assert sum(sizes) == steps and min(sizes) >= 1 and max(sizes) - min(sizes) <= 1
+    assert len(sizes) == max(1, min(rounds, steps))
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_dump_outputs_are_written_and_reproducible(tmp_path):
+    """--dump-outputs after a plain run: the last step's loss, parameters and gradients, float32 / float64, <= 64 MB,
+    and the same arrays from a second run with the same arguments (seeded inputs and weights, fixed step count)."""
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "LARVA_BENCH_DRY"):
+        env.pop(k, None)
+    dirs, losses = [], []
+    for i in range(2):
+        d = os.path.join(str(tmp_path), "run%d" % i)
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "4", "--warmup", "2", "--dump-outputs", d],
+                           env=env, capture_output=True, text=True, timeout=280)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
+        assert line["steps"] == 4 and line["ms_per_step"] > 0 and "roofline" not in line
+        dirs.append(d)
+        losses.append(line["config"]["final_loss"])
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1]))
+    assert "loss.npy" in names and any(n.startswith("param.") for n in names) and any(n.startswith("grad.") for n in names)
+    import numpy as np
+    total = 0
+    for n in names:
+        a, b = np.load(os.path.join(dirs[0], n)), np.load(os.path.join(dirs[1], n))
+        total += a.nbytes
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape, n
+        assert np.isfinite(a).all(), n
+        tol = 1e-5 * max(float(np.abs(a).max()), 1e-6)
+        assert float(np.abs(a.astype(np.float64) - b).max()) <= tol, n
+    assert 0 < total <= 64 << 20
+    for d, loss in zip(dirs, losses):   # (the line's final_loss is rounded to 6 digits)
+        assert abs(float(np.load(os.path.join(d, "loss.npy"))) - loss) <= 1e-5 * abs(loss)
