@@ -52,54 +52,6 @@ def _lw():
     return PaddedWidth.current
 
 
-class SideStreams:
-    """Concurrency inside one training step.  A conv launch keeps the matrix pipes busy only
-    about half of its duration (tile staging, the store burst and the launch floor are exposed),
-    and the conv / wgrad kernels are sized so that two workgroups share a CU -- so independent
-    work is put on side streams and the hardware overlaps it:
-      * `leg`:   exit i (leg convs + L1) runs beside body i+1, forward and -- because autograd
-                 replays a node on its forward stream -- backward;
-      * `wgrad`: weight-gradient batches (never on the critical path) run beside the dgrad chain.
-    Only active inside `with StepScope(side_streams=True):` (the plugin's forward+backward), which joins
-    every side stream before it returns; anywhere else everything stays on the current stream.
-    Tensors that a side stream still reads are kept referenced until the join, so the caching
-    allocator cannot hand their memory out early (also during hipGraph capture)."""
-
-    active = False
-    wgrad_on_side = False   # measured: wgrad alone already runs at 95 % of the MFMA peak and only
-                            # slows the conv chain down when it shares the CUs with it
-    _streams = {}
-    _keep = []
-
-    @classmethod
-    def get(cls, name):
-        dev = torch.cuda.current_device()
-        key = (dev, name)
-        if key not in cls._streams:
-            cls._streams[key] = torch.cuda.Stream(device=dev)
-        return cls._streams[key]
-
-    @classmethod
-    def fork(cls, name, *tensors):
-        """Side stream `name`, ordered after everything issued so far on the current stream."""
-        side = cls.get(name)
-        side.wait_stream(torch.cuda.current_stream())
-        cls._keep.extend(tensors)
-        return side
-
-    @classmethod
-    def keep(cls, *tensors):
-        cls._keep.extend(tensors)
-
-    @classmethod
-    def join(cls):
-        cur = torch.cuda.current_stream()
-        for (dev, _), st in cls._streams.items():
-            if dev == torch.cuda.current_device():
-                cur.wait_stream(st)
-        cls._keep.clear()
-
-
 class DualChain:
     """The dependent layer chain of a step (head -> 32 body convs forward, 32 dgrads backward) as TWO
     independent chains, one per half of the batch, on two streams.
@@ -122,11 +74,6 @@ class DualChain:
     hand its memory to a later allocation on the main stream)."""
 
     enabled = False      # set by StepScope
-    # output store policy of the strip launches: "fwd" = plain stores in the forward chain (read at once by
-    # the next launch), non-temporal in the backward chain; "all" / "none" for A/B timing
-    # round 4, same box, three alternating rounds (profiles/r04_ab_strip_plain.txt): all 1.634-1.641 ms, fwd 1.648-1.650,
-    # none 1.657-1.660 -- round 2's A/B (all-plain 1.696 against forward-only 1.688) no longer holds for today's kernels
-    plain_stores = os.environ.get("LARVA_STRIP_PLAIN", "all")
     lazy_fwd = False
     lazy_bwd = False
     max_workgroups = 512   # one full-batch launch with more 3 x 48 tiles than this already overlaps by itself
@@ -143,15 +90,14 @@ class DualChain:
             return False
         return K.strip_tile_table(h, p, torch.device("cuda", torch.cuda.current_device())) is not None
 
-    # Round 4: chain 0 runs on the stream that was current at the fork (the capture's own stream) and only chain 1 on a
-    # side stream: one cross-stream edge per fork and per join instead of two (each costs the dependent launch ~3-10 us,
-    # tools/step_marks.py).  LARVA_CHAIN0_ON_MAIN=0: both chains on side streams (rounds 2-3).
-    chain0_on_main = os.environ.get("LARVA_CHAIN0_ON_MAIN", "1") != "0"
+    # Chain 0 runs on the stream that was current at the fork (the capture's own stream) and only chain 1 on a side
+    # stream: one cross-stream edge per fork and per join instead of two (each costs the dependent launch ~3-10 us,
+    # tools/step_marks.py).
     _main = None
 
     @classmethod
     def _stream(cls, k):
-        if k == 0 and cls.chain0_on_main and cls._main is not None:
+        if k == 0 and cls._main is not None:
             return cls._main
         key = (torch.cuda.current_device(), k)
         if key not in cls._streams:
@@ -160,8 +106,10 @@ class DualChain:
 
     @classmethod
     def conv(cls, srcs, wpk, cout, forward=False, **kw):
-        """kernels.conv3x3 for a link of the chain (same arguments, `out` allocated here).  forward: a
-        link of the forward chain (its output is read by the next launch at once: plain stores)."""
+        """kernels.conv3x3 for a link of the chain (same arguments, `out` allocated here).  The strip launches
+        write their output with plain stores in both chains (same-box A/B, profiles/r04_ab_strip_plain.txt).
+        forward: a link of the forward chain; the conv ignores it, tools/step_marks.py reads it to label the
+        forward and backward phases of its timeline."""
         first = srcs if isinstance(srcs, torch.Tensor) else srcs[0]
         n, _, h, p = (int(v) for v in first.shape)
         if kw.get("logical_w") is not None or kw.get("shuffle") or not cls.wants(n, h, p):
@@ -182,7 +130,7 @@ class DualChain:
         half = n // 2
         for k, rng in enumerate(((0, half), (half, n))):
             with torch.cuda.stream(cls._stream(k)):
-                K.conv3x3(srcs, wpk, cout, out=out, images=rng, strips=2 if k else True, plain_stores=(cls.plain_stores == "all" or (forward and cls.plain_stores == "fwd")), **kw)
+                K.conv3x3(srcs, wpk, cout, out=out, images=rng, strips=2 if k else True, plain_stores=True, **kw)
         return out
 
     @classmethod
@@ -448,7 +396,7 @@ class DeferredWgrad:
     tensor handed back to autograd must be complete when backward() returns it."""
 
     active = False
-    jobs_per_launch = int(os.environ.get("LARVA_WGRAD_JOBS", "32"))
+    jobs_per_launch = 32   # layers per launch of a split flush (a flat grid takes as many as fit)
     _pending = {}   # (cout, cin) -> list of jobs (they keep dy / x / targets alive)
 
     # (Round 4, measured and removed: the exits' eight layers issued BESIDE the backward chain as a small grid on a
@@ -462,16 +410,12 @@ class DeferredWgrad:
 
     _late = []      # launches held back by a split flush: [(cout, cin, jobs)]
 
-    # one grid over all layers of a launch (kernels.conv3x3_wgrad_partial_flat) where the shape allows
-    flat = os.environ.get("LARVA_WGRAD_FLAT", "1") != "0"
-    head_in_flat = os.environ.get("LARVA_WGRAD_HEAD_IN_FLAT", "1") != "0"
-
     @classmethod
     def _launches(cls, split=False):
         pending, cls._pending = cls._pending, {}
-        cap = max(1, min(cls.jobs_per_launch, K.max_wgrad_jobs()))
-        if cls.flat and not split:
-            cap = K.max_wgrad_jobs()   # a flat grid has no preferred layer count: as many layers per launch as fit
+        # one grid over all layers of a launch (kernels.conv3x3_wgrad_partial_flat) has no preferred layer count: as
+        # many layers per launch as fit, except in a split flush
+        cap = max(1, min(cls.jobs_per_launch, K.max_wgrad_jobs())) if split else K.max_wgrad_jobs()
         out = []
         for (cout, cin), jobs in pending.items():
             # from the end of the gradient bucket downwards (= roughly the order backward produced
@@ -503,16 +447,15 @@ class DeferredWgrad:
         # the 3 -> 48 head (one (48, 16) layer on its padded input) rides at the end of the last flat (48, 48) grid
         # of the same image geometry instead of having a launch of its own
         head = host = None
-        if DeferredWgrad.flat and DeferredWgrad.head_in_flat:
-            heads = [l for l in launches if (l[0], l[1]) == (48, 16) and len(l[2]) == 1]
-            hosts = [l for l in launches if (l[0], l[1]) == (48, 48)]
-            if len(heads) == 1 and hosts and hosts[-1][2][0]["dy"].shape == heads[0][2][0]["dy"].shape:
-                head, host = heads[0], hosts[-1]
+        heads = [l for l in launches if (l[0], l[1]) == (48, 16) and len(l[2]) == 1]
+        hosts = [l for l in launches if (l[0], l[1]) == (48, 48)]
+        if len(heads) == 1 and hosts and hosts[-1][2][0]["dy"].shape == heads[0][2][0]["dy"].shape:
+            head, host = heads[0], hosts[-1]
         todo = [l for l in launches if l is not head]
         for launch in todo:   # (may grow: a head whose host grid did not apply goes its own way at the end)
             cout, cin, chunk = launch
             extra = head[2][0] if launch is host else None
-            res = K.conv3x3_wgrad_partial_flat(chunk, cout, cin, _WGRAD_WORKGROUPS, head=extra) if DeferredWgrad.flat else None
+            res = K.conv3x3_wgrad_partial_flat(chunk, cout, cin, _WGRAD_WORKGROUPS, head=extra)
             if res is None and extra is not None:
                 todo.append(head)
                 extra = None
@@ -560,9 +503,9 @@ class DeferredWgrad:
 
 
 class StepScope:
-    """The plugin's forward+backward of one batch: optional side streams, deferred wgrad.
-    Leaving the scope joins the side streams and issues the queued weight gradients, so they are
-    complete on the current stream afterwards (also as the tail of a hipGraph capture)."""
+    """The plugin's forward+backward of one batch: deferred wgrad, joint input gradients, the two layer chains.
+    Leaving the scope joins the chains and issues the queued weight gradients, so they are complete on
+    the current stream afterwards (also as the tail of a hipGraph capture)."""
 
     depth = 0
     _padded = {}
@@ -591,13 +534,12 @@ class StepScope:
             buf = cls._padded[key] = torch.zeros(shape, device=device, dtype=torch.float32)
         return buf
 
-    def __init__(self, side_streams=False, defer_wgrad=True, split_flush=False, joint_input_grads=True,
+    def __init__(self, defer_wgrad=True, split_flush=False, joint_input_grads=True,
                  seed_grad=None, dual_chain=False, lazy_chain_joins=(False, False), early_loss=False):
         self.seed_grad_value = seed_grad
         self.early_loss_value = early_loss or False
         self.dual_chain = dual_chain
         self.lazy_chain_joins = lazy_chain_joins
-        self.side_streams = side_streams
         self.defer_wgrad = defer_wgrad
         self.split_flush = split_flush
         self.joint_input_grads = joint_input_grads
@@ -605,13 +547,11 @@ class StepScope:
 
     def __enter__(self):
         gpu = torch.cuda.is_available()
-        SideStreams.active = bool(self.side_streams) and gpu
         DeferredWgrad.active = bool(self.defer_wgrad) and gpu
         DeferredWgrad.drop()
-        # (with side streams the exit and the next body run concurrently: keep them independent)
-        JointInputGrad.active = bool(self.joint_input_grads) and gpu and not SideStreams.active
+        JointInputGrad.active = bool(self.joint_input_grads) and gpu
         JointInputGrad.reset()
-        DualChain.enabled = bool(self.dual_chain) and gpu and not SideStreams.active
+        DualChain.enabled = bool(self.dual_chain) and gpu
         DualChain.lazy_fwd, DualChain.lazy_bwd = (bool(v) and DualChain.enabled for v in self.lazy_chain_joins)
         StepScope.depth += 1
         StepScope.seed_grad = self.seed_grad_value
@@ -621,8 +561,6 @@ class StepScope:
     def __exit__(self, exc_type, *exc):
         try:
             DualChain.join()   # the dgrad chains end here; the queued weight gradients read what they wrote
-            if SideStreams.active:
-                SideStreams.join()
             if exc_type is None:
                 self.early_targets = DeferredWgrad.flush(split=self.split_flush)
                 DeferredWgrad.finish_loss()
@@ -636,7 +574,6 @@ class StepScope:
             StepScope.seed_grad = None
             StepScope.early_loss = False
             DeferredWgrad._pending = {}
-            SideStreams.active = False
             DualChain.enabled = DualChain.lazy_fwd = DualChain.lazy_bwd = False
             DeferredWgrad.active = False
             JointInputGrad.active = False
@@ -647,44 +584,27 @@ class StepScope:
 def _wgrad(jobs, cout, cin, inplace=False):
     """jobs: list of (dy, x, weight shape, cin_off, cin_valid, shared dw or None[, shared db]) ->
     list of (dw, db).  inplace: every dw/db that matters is a GradBucket view, so the whole
-    job may be deferred to the end of the StepScope.  Inside a SideStreams scope with
-    wgrad_on_side the launches go to the wgrad side stream."""
-    side = None
-    if SideStreams.active and SideStreams.wgrad_on_side:
-        side = SideStreams.fork("wgrad", *[t for j in jobs for t in (j[0], j[1])])
-    defer = inplace and DeferredWgrad.active and side is None
-    jobs = list(jobs)
-    ctx = torch.cuda.stream(side) if side is not None else _NullCtx()
+    job may be deferred to the end of the StepScope."""
+    defer = inplace and DeferredWgrad.active
     out, batch = [], []
-    with ctx:
-        for job in jobs:
-            (dy, x, wshape, cin_off, cin_valid, dw_shared) = job[:6]
-            db_shared = job[6] if len(job) > 6 else None
-            dw = dw_shared if dw_shared is not None else torch.empty(wshape, device=dy.device, dtype=torch.float32)
-            if db_shared is not None or not defer:
-                db = db_shared if db_shared is not None else torch.empty((cout,), device=dy.device,
-                                                                         dtype=torch.float32)
-            else:
-                db = None  # in-place mode and nobody wants this bias gradient
-            batch.append({"dy": dy, "x": x, "dw": dw, "db": db, "cin_off": cin_off, "cin_valid": cin_valid})
-            out.append((dw, db))
-        if defer:
-            DeferredWgrad.push(cout, cin, batch)
-            batch = []
-        for i in range(0, len(batch), 16):
-            chunk = batch[i:i + 16]
-            parts = K.conv3x3_wgrad(chunk, cout, cin, _splits(len(chunk), cout, cin))
-            if side is not None:
-                SideStreams.keep(*parts)
+    for job in jobs:
+        (dy, x, wshape, cin_off, cin_valid, dw_shared) = job[:6]
+        db_shared = job[6] if len(job) > 6 else None
+        dw = dw_shared if dw_shared is not None else torch.empty(wshape, device=dy.device, dtype=torch.float32)
+        if db_shared is not None or not defer:
+            db = db_shared if db_shared is not None else torch.empty((cout,), device=dy.device,
+                                                                     dtype=torch.float32)
+        else:
+            db = None  # in-place mode and nobody wants this bias gradient
+        batch.append({"dy": dy, "x": x, "dw": dw, "db": db, "cin_off": cin_off, "cin_valid": cin_valid})
+        out.append((dw, db))
+    if defer:
+        DeferredWgrad.push(cout, cin, batch)
+        batch = []
+    for i in range(0, len(batch), 16):
+        chunk = batch[i:i + 16]
+        K.conv3x3_wgrad(chunk, cout, cin, _splits(len(chunk), cout, cin))
     return out
-
-
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
 
 
 # ONE rule for "a large inference batch" (a whole validation image rather than a batch of patches): above it the
@@ -970,8 +890,6 @@ class ExitsFn(torch.autograd.Function):
     Backward leaves the input gradient of every exit whose leg shares its input with the next
     body's first conv to that body (JointInputGrad)."""
 
-    fuse_l1 = os.environ.get("LARVA_FUSE_EXIT_L1", "1") != "0"   # L1 inside the pixel-shuffle conv launch
-
     @staticmethod
     def forward(ctx, base, truth, legs, divisor, *args):
         M = len(legs)  # legs: [[PackedConv conv1, PackedConv conv2]] per exit
@@ -985,7 +903,7 @@ class ExitsFn(torch.autograd.Function):
         shuffle_jobs = [{"srcs": hs[i], "wpk": legs[i][1].get()[0][0], "bias": params[4 * i + 3].detach(), "base": base}
                         for i in range(M)]
         outs, parts, third = [None] * M, [None] * M, [None] * M
-        fused = ctx.have_dyl and ExitsFn.fuse_l1
+        fused = ctx.have_dyl
         if fused:
             # gradient value known now: every exit is scored inside its pixel-shuffle conv launch (partial
             # sums of |out - truth| and the sign gradient straight from the accumulators); only the last

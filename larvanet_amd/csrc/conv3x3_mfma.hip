@@ -1345,156 +1345,115 @@ struct LaunchTiming {
   hipEvent_t start, stop;
 };
 
-template <int COUT, bool VEC, int EPI>
-static hipError_t launch_conv_e(const ConvArgs& a, hipStream_t stream, const LaunchTiming* tm) {
-  using C = ConvCfg<COUT>;
-  constexpr size_t lds = VEC ? C::LDS_BYTES_DMA : C::LDS_BYTES_REG;
+// One launch of `Kernel`: its dynamic-LDS attribute set once per device (ensure_dynamic_lds, one PerDeviceOnce per
+// kernel instantiation), then with the kernel-attached events of `tm` when given.
+template <auto Kernel, typename Args>
+static hipError_t launch(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const LaunchTiming* tm, const Args& a) {
   static PerDeviceOnce lds_set;
-  if (const hipError_t e = ensure_dynamic_lds(lds_set, reinterpret_cast<const void*>(conv3x3_mfma_kernel<COUT, VEC, EPI>), lds); e != hipSuccess) return e;
-  const int grid = a.N * a.tiles_x * a.tiles_y;
-  constexpr int threads = VEC ? C::THREADS_DMA : 256;
+  if (const hipError_t e = ensure_dynamic_lds(lds_set, reinterpret_cast<const void*>(Kernel), lds); e != hipSuccess) return e;
   if (tm)
-    hipExtLaunchKernelGGL((conv3x3_mfma_kernel<COUT, VEC, EPI>), dim3(grid), dim3(threads), lds, stream,
-                          tm->start, tm->stop, 0, a);
+    hipExtLaunchKernelGGL(Kernel, grid, block, lds, stream, tm->start, tm->stop, 0, a);
   else
-    hipLaunchKernelGGL((conv3x3_mfma_kernel<COUT, VEC, EPI>), dim3(grid), dim3(threads), lds, stream, a);
+    hipLaunchKernelGGL(Kernel, grid, block, lds, stream, a);
   return hipGetLastError();
 }
 
-template <int COUT, int EPI>
-static hipError_t launch_rows4_e(const ConvArgs& a, hipStream_t stream, const LaunchTiming* tm) {
-  using C = ConvCfg<COUT, GeoWide4>;
-  constexpr size_t lds = C::LDS_BYTES_DMA;
-  static PerDeviceOnce lds_set;
-  if (const hipError_t e = ensure_dynamic_lds(lds_set, reinterpret_cast<const void*>(conv3x3_mfma_rows4_kernel<COUT, EPI>), lds); e != hipSuccess) return e;
-  if (tm)
-    hipExtLaunchKernelGGL((conv3x3_mfma_rows4_kernel<COUT, EPI>), dim3(a.nwg), dim3(C::THREADS_DMA), lds, stream,
-                          tm->start, tm->stop, 0, a);
-  else
-    hipLaunchKernelGGL((conv3x3_mfma_rows4_kernel<COUT, EPI>), dim3(a.nwg), dim3(C::THREADS_DMA), lds, stream, a);
-  return hipGetLastError();
+// The epilogues a tiling is compiled for.
+template <int... E>
+struct EpiSet {
+  static constexpr bool has(int epi) { return ((epi == E) || ...); }
+};
+// per-tile, strip and batch tiles: every epilogue of a forward or backward conv
+using EpiAll = EpiSet<kEpiPlain, kEpiRelu, kEpiMask, kEpiRes1, kEpiRes2, kEpiShuffle, kEpiShuffleBase>;
+// the batch tiles at 48 channels add the exits' fused L1
+using EpiBatch48 = EpiSet<kEpiPlain, kEpiRelu, kEpiMask, kEpiRes1, kEpiRes2, kEpiShuffle, kEpiShuffleBase, kEpiShuffleL1>;
+// the epilogues of an inference forward (head, conv + ReLU, the two residual forms, the pixel-shuffle exits)
+using EpiInference = EpiSet<kEpiPlain, kEpiRelu, kEpiRes1, kEpiRes2, kEpiShuffle, kEpiShuffleBase>;
+using EpiRows4 = EpiInference;     // 4 x 48 tiles
+using EpiPersist = EpiInference;   // persistent workgroups
+
+// f(std::integral_constant<int, E>{}) for the member E == epi of the set; `absent` when epi is not one of them
+template <int... E, typename F>
+static hipError_t with_epi(EpiSet<E...>, int epi, hipError_t absent, F&& f) {
+  hipError_t r = absent;
+  (void)((epi == E && (r = f(std::integral_constant<int, E>{}), true)) || ...);
+  return r;
+}
+
+// f(std::integral_constant<int, COUT>{}) for cout = 32, 48 or 64 (48 alone in a LARVA_DIAG_ONLY48 build); `absent`
+// for any other cout
+template <typename F>
+static hipError_t with_cout(int cout, hipError_t absent, F&& f) {
+  switch (cout) {
+#if !LARVA_DIAG_ONLY48
+    case 32: return f(std::integral_constant<int, 32>{});
+    case 64: return f(std::integral_constant<int, 64>{});
+#endif
+    case 48: return f(std::integral_constant<int, 48>{});
+    default: return absent;
+  }
 }
 
 // workgroup slots of the device for the 16-byte-path kernels (kWgPerCu per CU)
 static int conv_slots() { return kWgPerCu * device_cu_count(); }
 
-template <int COUT, int EPI>
-static hipError_t launch_persist_e(const ConvArgs& a, hipStream_t stream, const LaunchTiming* tm) {
-  using C = ConvCfg<COUT>;
-  constexpr size_t lds = C::LDS_BYTES_DMA;
-  static PerDeviceOnce lds_set;
-  if (const hipError_t e = ensure_dynamic_lds(lds_set, reinterpret_cast<const void*>(conv3x3_mfma_persist_kernel<COUT, EPI>), lds); e != hipSuccess) return e;
-  const int grid = a.nwg < conv_slots() ? a.nwg : conv_slots();
-  if (tm)
-    hipExtLaunchKernelGGL((conv3x3_mfma_persist_kernel<COUT, EPI>), dim3(grid), dim3(C::THREADS_DMA), lds, stream, tm->start, tm->stop, 0, a);
-  else
-    hipLaunchKernelGGL((conv3x3_mfma_persist_kernel<COUT, EPI>), dim3(grid), dim3(C::THREADS_DMA), lds, stream, a);
-  return hipGetLastError();
-}
-
-// persistent tiles exist for the epilogues of an inference forward; anything else: hipErrorNotSupported
-template <int COUT>
-static hipError_t launch_persist(const ConvArgs& a, int epi, hipStream_t stream, const LaunchTiming* tm) {
-  // (the residual / mask operands of these kernels come by buffer loads with 32-bit byte offsets inside one image)
-  if ((long long)COUT * a.H * a.pitch * 4 >= (1ll << 31)) return hipErrorNotSupported;
-  switch (epi) {
-    case kEpiPlain: return launch_persist_e<COUT, kEpiPlain>(a, stream, tm);
-    case kEpiRelu: return launch_persist_e<COUT, kEpiRelu>(a, stream, tm);
-    case kEpiRes1: return launch_persist_e<COUT, kEpiRes1>(a, stream, tm);
-    case kEpiRes2: return launch_persist_e<COUT, kEpiRes2>(a, stream, tm);
-    case kEpiShuffle: return launch_persist_e<COUT, kEpiShuffle>(a, stream, tm);
-    case kEpiShuffleBase: return launch_persist_e<COUT, kEpiShuffleBase>(a, stream, tm);
-    default: return hipErrorNotSupported;
-  }
-}
-
-// 4 x 48 tiles exist for the epilogues of an inference forward (head, conv + ReLU, the two residual forms, the
-// pixel-shuffle exits); anything else: hipErrorNotSupported, the caller launches the 3 x 48 tiles
-template <int COUT>
-static hipError_t launch_rows4(const ConvArgs& a, int epi, hipStream_t stream, const LaunchTiming* tm) {
-  switch (epi) {
-    case kEpiPlain: return launch_rows4_e<COUT, kEpiPlain>(a, stream, tm);
-    case kEpiRelu: return launch_rows4_e<COUT, kEpiRelu>(a, stream, tm);
-    case kEpiRes1: return launch_rows4_e<COUT, kEpiRes1>(a, stream, tm);
-    case kEpiRes2: return launch_rows4_e<COUT, kEpiRes2>(a, stream, tm);
-    case kEpiShuffle: return launch_rows4_e<COUT, kEpiShuffle>(a, stream, tm);
-    case kEpiShuffleBase: return launch_rows4_e<COUT, kEpiShuffleBase>(a, stream, tm);
-    default: return hipErrorNotSupported;
-  }
-}
-
-template <int COUT, bool VEC>
-static hipError_t launch_conv_v(const ConvArgs& a, int epi, hipStream_t stream, const LaunchTiming* tm) {
-  switch (epi) {
-    case kEpiPlain: return launch_conv_e<COUT, VEC, kEpiPlain>(a, stream, tm);
-    case kEpiRelu: return launch_conv_e<COUT, VEC, kEpiRelu>(a, stream, tm);
-    case kEpiMask: return launch_conv_e<COUT, VEC, kEpiMask>(a, stream, tm);
-    case kEpiRes1: return launch_conv_e<COUT, VEC, kEpiRes1>(a, stream, tm);
-    case kEpiRes2: return launch_conv_e<COUT, VEC, kEpiRes2>(a, stream, tm);
-    case kEpiShuffle: return launch_conv_e<COUT, VEC, kEpiShuffle>(a, stream, tm);
-    case kEpiShuffleBase: return launch_conv_e<COUT, VEC, kEpiShuffleBase>(a, stream, tm);
-    default: return hipErrorInvalidValue;
-  }
-}
-
+// one workgroup per 3 x 48 tile; an epilogue outside the set: hipErrorInvalidValue
 template <int COUT>
 static hipError_t launch_conv(const ConvArgs& a, bool vec, int epi, hipStream_t stream, const LaunchTiming* tm) {
-  return vec ? launch_conv_v<COUT, true>(a, epi, stream, tm) : launch_conv_v<COUT, false>(a, epi, stream, tm);
-}
-
-template <int COUT, int EPI>
-static hipError_t launch_batch_e(const ConvBatch& b, int njobs, hipStream_t stream) {
   using C = ConvCfg<COUT>;
-  static PerDeviceOnce lds_set;
-  if (const hipError_t e = ensure_dynamic_lds(lds_set, reinterpret_cast<const void*>(conv3x3_mfma_batch_kernel<COUT, EPI>), C::LDS_BYTES_DMA); e != hipSuccess) return e;
-  const ConvArgs& a = b.job[0];
-  hipLaunchKernelGGL((conv3x3_mfma_batch_kernel<COUT, EPI>), dim3(a.N * a.tiles_x * a.tiles_y, njobs),
-                     dim3(C::THREADS_DMA), C::LDS_BYTES_DMA, stream, b);
-  return hipGetLastError();
+  const dim3 grid(a.N * a.tiles_x * a.tiles_y);
+  return with_epi(EpiAll{}, epi, hipErrorInvalidValue, [&](auto e) {
+    constexpr int EPI = decltype(e)::value;
+    if (vec)
+      return launch<conv3x3_mfma_kernel<COUT, true, EPI>>(grid, dim3(C::THREADS_DMA), C::LDS_BYTES_DMA, stream, tm, a);
+    return launch<conv3x3_mfma_kernel<COUT, false, EPI>>(grid, dim3(256), C::LDS_BYTES_REG, stream, tm, a);
+  });
 }
 
+// 4 x 48 tiles (a.nwg of them); an epilogue outside the set: hipErrorNotSupported, the caller launches the 3 x 48 tiles
+template <int COUT>
+static hipError_t launch_rows4(const ConvArgs& a, int epi, hipStream_t stream, const LaunchTiming* tm) {
+  using C = ConvCfg<COUT, GeoWide4>;
+  return with_epi(EpiRows4{}, epi, hipErrorNotSupported, [&](auto e) {
+    return launch<conv3x3_mfma_rows4_kernel<COUT, decltype(e)::value>>(dim3(a.nwg), dim3(C::THREADS_DMA), C::LDS_BYTES_DMA,
+                                                                      stream, tm, a);
+  });
+}
+
+// persistent workgroups, one per slot; an epilogue outside the set: hipErrorNotSupported
+template <int COUT>
+static hipError_t launch_persist(const ConvArgs& a, int epi, hipStream_t stream, const LaunchTiming* tm) {
+  using C = ConvCfg<COUT>;
+  // (the residual / mask operands of these kernels come by buffer loads with 32-bit byte offsets inside one image)
+  if ((long long)COUT * a.H * a.pitch * 4 >= (1ll << 31)) return hipErrorNotSupported;
+  const int grid = a.nwg < conv_slots() ? a.nwg : conv_slots();
+  return with_epi(EpiPersist{}, epi, hipErrorNotSupported, [&](auto e) {
+    return launch<conv3x3_mfma_persist_kernel<COUT, decltype(e)::value>>(dim3(grid), dim3(C::THREADS_DMA), C::LDS_BYTES_DMA,
+                                                                        stream, tm, a);
+  });
+}
+
+// njobs x the per-tile grid; kEpiShuffleL1 at another cout than 48: hipErrorNotSupported, an epilogue outside the set
+// hipErrorInvalidValue
 template <int COUT>
 static hipError_t launch_batch(const ConvBatch& b, int njobs, int epi, hipStream_t stream) {
-  switch (epi) {
-    case kEpiPlain: return launch_batch_e<COUT, kEpiPlain>(b, njobs, stream);
-    case kEpiRelu: return launch_batch_e<COUT, kEpiRelu>(b, njobs, stream);
-    case kEpiMask: return launch_batch_e<COUT, kEpiMask>(b, njobs, stream);
-    case kEpiRes1: return launch_batch_e<COUT, kEpiRes1>(b, njobs, stream);
-    case kEpiRes2: return launch_batch_e<COUT, kEpiRes2>(b, njobs, stream);
-    case kEpiShuffle: return launch_batch_e<COUT, kEpiShuffle>(b, njobs, stream);
-    case kEpiShuffleBase: return launch_batch_e<COUT, kEpiShuffleBase>(b, njobs, stream);
-    case kEpiShuffleL1:
-      if constexpr (COUT == 48) return launch_batch_e<COUT, kEpiShuffleL1>(b, njobs, stream);
-      return hipErrorNotSupported;
-    default: return hipErrorInvalidValue;
-  }
+  using C = ConvCfg<COUT>;
+  using Set = std::conditional_t<COUT == 48, EpiBatch48, EpiAll>;
+  const ConvArgs& a = b.job[0];
+  return with_epi(Set{}, epi, epi == kEpiShuffleL1 ? hipErrorNotSupported : hipErrorInvalidValue, [&](auto e) {
+    return launch<conv3x3_mfma_batch_kernel<COUT, decltype(e)::value>>(dim3(a.N * a.tiles_x * a.tiles_y, njobs),
+                                                                      dim3(C::THREADS_DMA), C::LDS_BYTES_DMA, stream,
+                                                                      nullptr, b);
+  });
 }
 
-template <int COUT, int EPI>
-static hipError_t launch_strip_e(const ConvArgs& a, hipStream_t stream, const LaunchTiming* tm) {
-  constexpr size_t lds = kStripLdsBytes<COUT>;
-  static PerDeviceOnce lds_set;
-  if (const hipError_t e = ensure_dynamic_lds(lds_set, reinterpret_cast<const void*>(conv3x3_mfma_strip_kernel<COUT, EPI>), lds); e != hipSuccess) return e;
-  if (tm)
-    hipExtLaunchKernelGGL((conv3x3_mfma_strip_kernel<COUT, EPI>), dim3(a.nwg), dim3(320), lds, stream,
-                          tm->start, tm->stop, 0, a);
-  else
-    hipLaunchKernelGGL((conv3x3_mfma_strip_kernel<COUT, EPI>), dim3(a.nwg), dim3(320), lds, stream, a);
-  return hipGetLastError();
-}
-
+// strip tiles (a.nwg of them); an epilogue outside the set: hipErrorInvalidValue
 template <int COUT>
-static hipError_t launch_strip(const ConvArgs& a, int epi, hipStream_t stream, const LaunchTiming* tm = nullptr) {
-  switch (epi) {
-    case kEpiPlain: return launch_strip_e<COUT, kEpiPlain>(a, stream, tm);
-    case kEpiRelu: return launch_strip_e<COUT, kEpiRelu>(a, stream, tm);
-    case kEpiMask: return launch_strip_e<COUT, kEpiMask>(a, stream, tm);
-    case kEpiRes1: return launch_strip_e<COUT, kEpiRes1>(a, stream, tm);
-    case kEpiRes2: return launch_strip_e<COUT, kEpiRes2>(a, stream, tm);
-    case kEpiShuffle: return launch_strip_e<COUT, kEpiShuffle>(a, stream, tm);
-    case kEpiShuffleBase: return launch_strip_e<COUT, kEpiShuffleBase>(a, stream, tm);
-    default: return hipErrorInvalidValue;
-  }
+static hipError_t launch_strip(const ConvArgs& a, int epi, hipStream_t stream, const LaunchTiming* tm) {
+  return with_epi(EpiAll{}, epi, hipErrorInvalidValue, [&](auto e) {
+    return launch<conv3x3_mfma_strip_kernel<COUT, decltype(e)::value>>(dim3(a.nwg), dim3(320), kStripLdsBytes<COUT>, stream,
+                                                                      tm, a);
+  });
 }
 
 }  // namespace larva
@@ -1646,8 +1605,7 @@ static int conv_build(const float* const* src, int n_src, int cin_per_src, const
 // 65.1 against 64.0 us -- the "fewer rounds" argument (935 instead of 1243 tiles) does not hold, workgroups are placed
 // as slots free up, not in rounds.  So: 4 rows for 32-channel launches of more than one round's worth of tiles.
 static int conv_tile_rows(int N, int H, int pitch, int cout, int epi, bool aligned, int forced) {
-  const bool can4 = aligned && (cout == 48 || cout == 32) &&
-                    (epi == kEpiPlain || epi == kEpiRelu || epi == kEpiRes1 || epi == kEpiRes2 || epi == kEpiShuffle || epi == kEpiShuffleBase);
+  const bool can4 = aligned && (cout == 48 || cout == 32) && EpiRows4::has(epi);
   if (forced == 3 || !can4) return 3;
   if (forced == 4) return 4;
   const long long tiles3 = (long long)N * ((pitch + kTileCols - 1) / kTileCols) * ((H + 2) / 3);
@@ -1670,10 +1628,10 @@ static int conv_dispatch(const float* const* src, int n_src, int cin_per_src, co
     a.tiles_y = (H + 3) / 4;
     a.magic_ty = div_magic(a.tiles_y);
     a.nwg = N * a.tiles_x * a.tiles_y;
-#if !LARVA_DIAG_ONLY48
-    if (cout == 32) return (int)launch_rows4<32>(a, epi, s, tm);
-#endif
-    return (int)launch_rows4<48>(a, epi, s, tm);
+    return (int)with_cout(cout, hipErrorInvalidValue, [&](auto c) {
+      if constexpr (decltype(c)::value == 64) return hipErrorNotSupported;   // (no 4 x 48 tiles: conv_tile_rows never asks)
+      else return launch_rows4<decltype(c)::value>(a, epi, s, tm);
+    });
   }
   if (tile_rows == 4) return (int)hipErrorNotSupported;
   // more tiles than workgroup slots (a full image): one persistent workgroup per slot (conv3x3_mfma_persist_kernel)
@@ -1681,25 +1639,14 @@ static int conv_dispatch(const float* const* src, int n_src, int cin_per_src, co
   const char* pe = getenv("LARVA_PERSIST");
   const bool persist_on = !(pe && pe[0] == '0');
   if (persist_on && aligned && a.nwg > conv_slots()) {
-    hipError_t e = hipErrorNotSupported;
-    switch (cout) {
-#if !LARVA_DIAG_ONLY48
-      case 32: e = launch_persist<32>(a, epi, s, tm); break;
-      case 64: e = launch_persist<64>(a, epi, s, tm); break;
-#endif
-      case 48: e = launch_persist<48>(a, epi, s, tm); break;
-      default: break;
-    }
+    const hipError_t e = with_cout(cout, hipErrorNotSupported, [&](auto c) {
+      return launch_persist<decltype(c)::value>(a, epi, s, tm);
+    });
     if (e != hipErrorNotSupported) return (int)e;
   }
-  switch (cout) {
-#if !LARVA_DIAG_ONLY48
-    case 32: return (int)launch_conv<32>(a, aligned, epi, s, tm);
-    case 64: return (int)launch_conv<64>(a, aligned, epi, s, tm);
-#endif
-    case 48: return (int)launch_conv<48>(a, aligned, epi, s, tm);
-    default: return (int)hipErrorInvalidValue;
-  }
+  return (int)with_cout(cout, hipErrorInvalidValue, [&](auto c) {
+    return launch_conv<decltype(c)::value>(a, aligned, epi, s, tm);
+  });
 }
 
 int larva_conv3x3_fwd(const float* const* src, int n_src, int cin_per_src, const float* wpk,
@@ -1758,15 +1705,9 @@ int larva_conv3x3_fwd_batch(int njobs, const float* const* src, int n_src, int c
     if (j > 0 && epi != epi0) return (int)hipErrorInvalidValue;
     epi0 = epi;
   }
-  hipStream_t s = (hipStream_t)stream;
-  switch (cout) {
-#if !LARVA_DIAG_ONLY48
-    case 32: return (int)launch_batch<32>(b, njobs, epi0, s);
-    case 64: return (int)launch_batch<64>(b, njobs, epi0, s);
-#endif
-    case 48: return (int)launch_batch<48>(b, njobs, epi0, s);
-    default: return (int)hipErrorInvalidValue;
-  }
+  return (int)with_cout(cout, hipErrorInvalidValue, [&](auto c) {
+    return launch_batch<decltype(c)::value>(b, njobs, epi0, (hipStream_t)stream);
+  });
 }
 
 // njobs (2..4) EXITS of the training step in one launch (models/LarvaNet.py:104-109 for several i):
@@ -1900,11 +1841,9 @@ static int strips_dispatch(const float* const* src, int n_src, int cin_per_src, 
   a.magic_tx = div_magic(tiles_per_image);
   a.magic_ty = div_magic(1);
   a.nwg = N * tiles_per_image;
-#if !LARVA_DIAG_ONLY48
-  if (cout == 32) return (int)launch_strip<32>(a, epi, (hipStream_t)stream, tm);
-  if (cout == 64) return (int)launch_strip<64>(a, epi, (hipStream_t)stream, tm);
-#endif
-  return (int)launch_strip<48>(a, epi, (hipStream_t)stream, tm);
+  return (int)with_cout(cout, hipErrorNotSupported, [&](auto c) {
+    return launch_strip<decltype(c)::value>(a, epi, (hipStream_t)stream, tm);
+  });
 }
 
 int larva_conv3x3_fwd_strips(const float* const* src, int n_src, int cin_per_src, const float* wpk,

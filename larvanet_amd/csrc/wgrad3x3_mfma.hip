@@ -26,8 +26,6 @@
 #include "larva_common.h"
 #include "larva_loss.h"
 
-#include <stdlib.h>
-
 #include <type_traits>
 
 // Timing-only ablations of the pipelined kernel (tools/diag_wgrad.py): 1 no MFMA, 2 no staging
@@ -1193,14 +1191,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(ReduceBatch rb) {
   }
 }
 
-static bool wgrad_use_pipe() {
-  static const bool on = [] {
-    const char* e = getenv("LARVA_WGRAD_PIPE");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
 // How a (COUT, CIN) layer gets onto the pipelined kernel: 1 = as it is, 2 = as two passes over 32 input channels each
 // ((64, 64) and the 64-filter legs' (48, 64): two tile buffers of the whole layer do not fit the LDS), 0 = not at all.
 template <int COUT, int CIN>
@@ -1211,7 +1201,7 @@ static hipError_t launch_wgrad(const WgradBatch& b, int njobs, int splits, hipSt
   using C = WgCfg<COUT, CIN>;
   using P = WgPipe<COUT, CIN>;
   if constexpr (kPipeHalves<COUT, CIN> == 2) {
-    if (b.vec_ok && wgrad_use_pipe()) {
+    if (b.vec_ok) {
       using P2 = WgPipe<COUT, CIN / 2>;
       static PerDeviceOnce lds_half;
       if (const hipError_t e = ensure_dynamic_lds(lds_half, reinterpret_cast<const void*>(wgrad3x3_pipe_kernel<COUT, CIN / 2>), P2::LDS_BYTES);
@@ -1233,7 +1223,7 @@ static hipError_t launch_wgrad(const WgradBatch& b, int njobs, int splits, hipSt
       return e;
   }
   if constexpr (P::FITS) {
-    if (b.vec_ok && wgrad_use_pipe()) {
+    if (b.vec_ok) {
       hipLaunchKernelGGL((wgrad3x3_pipe_kernel<COUT, CIN>), dim3(splits, njobs), dim3(256), P::LDS_BYTES, stream, b);
       return hipGetLastError();
     }
@@ -1288,7 +1278,7 @@ static int wgrad_flat_impl(const float* const* dy, const float* const* x, float*
                            int cin, int H, int W, int* splits_out, int* head_splits_out, void* stream) {
   if (njobs < 1 || njobs > kMaxJobs || nwg < 1 || nwg > 32767 || N <= 0 || H <= 0 || W <= 0 || !splits_out)
     return (int)hipErrorInvalidValue;
-  if (!((cout == 48 && cin == 48) || (cout == 32 && cin == 32) || (cout == 64 && cin == 64)) || W % 4 || !wgrad_use_pipe())
+  if (!((cout == 48 && cin == 48) || (cout == 32 && cin == 32) || (cout == 64 && cin == 64)) || W % 4)
     return (int)hipErrorNotSupported;
   const bool head = head_dy || head_x16 || head_partial;
   if (head && cout != 48) return (int)hipErrorNotSupported;   // (the head's tail role is priced for the 48-channel grid)
@@ -1393,11 +1383,11 @@ int larva_conv3x3_wgrad_partial_flat_head(const float* const* dy, const float* c
 // full launches 256 * this many workgroups in total.
 int larva_wgrad_cu_share(int cout, int cin) {
   if (cout == 48 && cin == 48) return 1;   // (the pipelined kernel: 159 KB of LDS)
-  if (cout == 32 && cin == 32) return (WgPipe<32, 32>::FITS && wgrad_use_pipe()) ? 1 : kWgradPerCu<32, 32>;
+  if (cout == 32 && cin == 32) return WgPipe<32, 32>::FITS ? 1 : kWgradPerCu<32, 32>;
   // (the pipelined kernel, where a shape is on it, owns its CU: two tile buffers)
-  if (cout == 48 && cin == 16) return (WgPipe<48, 16>::FITS && wgrad_use_pipe()) ? 1 : kWgradPerCu<48, 16>;
-  if (cout == 32 && cin == 16) return (WgPipe<32, 16>::FITS && wgrad_use_pipe()) ? 1 : kWgradPerCu<32, 16>;
-  if (cout == 64 && cin == 16) return (WgPipe<64, 16>::FITS && wgrad_use_pipe()) ? 1 : kWgradPerCu<64, 16>;
+  if (cout == 48 && cin == 16) return WgPipe<48, 16>::FITS ? 1 : kWgradPerCu<48, 16>;
+  if (cout == 32 && cin == 16) return WgPipe<32, 16>::FITS ? 1 : kWgradPerCu<32, 16>;
+  if (cout == 64 && cin == 16) return WgPipe<64, 16>::FITS ? 1 : kWgradPerCu<64, 16>;
   return 1;
 }
 

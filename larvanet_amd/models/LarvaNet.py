@@ -21,7 +21,7 @@ import torch.nn as nn
 from .. import dist as ldist
 from .. import kernels as K
 from ..autograd import (BodyFn, DualChain, ExitFn, ExitsFn, GradBucket, HeadFn, L1LossFn, LegFn, LossTerm, PackedConv, PaddedWidth, mean_of_terms,
-                        SideStreams, StepScope, is_large_inference, pack_all)
+                        StepScope, is_large_inference, pack_all)
 from ..autograd import step_prologue as autograd_step_prologue
 from ..optim import FlatAdamW, flatten_parameters
 from ..metrics import image_psnr, image_to_uint8, fit_truth_image_size
@@ -261,17 +261,12 @@ class LarvaNet(BaseModel):
         # a failed capture raises instead of continuing ~2.4x slower with a printed warning: the drivers
         # (train_larva.py / validate.py / runtime.py) set it unless --allow_eager_fallback, bench.py exits on a fallback
         self.strict_graph = os.environ.get("LARVA_HIP_GRAPH_STRICT", "0") != "0"
-        # Exits on a side stream: measured neutral-to-negative on MI355X at batch 16 (same-box A/B:
-        # 2.36 ms without, 2.36 / 2.45 ms with, depending on the wgrad variant) -- opt-in.
-        self.use_side_streams = os.environ.get("LARVA_SIDE_STREAMS", "0") != "0"
         # weight gradients of all layers in a few large launches at the end of backward
         self.defer_wgrad = os.environ.get("LARVA_DEFER_WGRAD", "1") != "0"
         # one dgrad launch for the two convs that read the same body output (next body + this exit)
         self.joint_input_grads = os.environ.get("LARVA_JOINT_DGRAD", "1") != "0"
         # all exits as one autograd node whose convs go out as batched launches (ExitsFn)
         self.batch_exits = os.environ.get("LARVA_BATCH_EXITS", "1") != "0"
-        # the exits' L1 gradient is written by the forward sweep that computes the L1 value
-        self.l1_grad_in_forward = os.environ.get("LARVA_L1_GRAD_FWD", "1") != "0"
         # data parallel: all-reduce the first half of the bucket beside the second half's wgrad kernels.  "auto" (the
         # default): decided once at prepare() from a timed isolated all-reduce of the bucket (_choose_dp_schedule)
         self.overlap_allreduce = {"0": False, "1": True}.get(os.environ.get("LARVA_OVERLAP_ALLREDUCE", "auto"), "auto")
@@ -400,7 +395,7 @@ class LarvaNet(BaseModel):
     def _num_loss_terms(self):
         return self.args.num_modules
 
-    def _exit_fused(self, leg, fea, base, truth_tensor):
+    def _exit(self, leg, fea, base, truth_tensor):
         """leg(fea, base) and loss_fn(out, truth) as one autograd node (ExitFn) when loss_fn is
         the stock L1Loss; otherwise the two separate calls of the reference.  Returns (image, term):
         in the fused case the term is a LossTerm of partial sums that the mean over the exits
@@ -415,28 +410,10 @@ class LarvaNet(BaseModel):
         out = leg(fea, base)
         return out, self.loss_fn(out, truth_tensor)
 
-    def _exit(self, leg, fea, base, truth_tensor):
-        """One exit (leg + its L1 term); on the `leg` side stream when side streams are active, so
-        that it overlaps the next body (forward) and the previous body's backward."""
-        if not SideStreams.active:
-            return self._exit_fused(leg, fea, base, truth_tensor)
-        side = SideStreams.fork("leg", fea, base, truth_tensor)
-        with torch.cuda.stream(side):
-            out, term = self._exit_fused(leg, fea, base, truth_tensor)
-        SideStreams.keep(out, term.tensor if isinstance(term, LossTerm) else term)
-        self._pending_exit_sync = True
-        return out, term
-
-    def _sync_exits(self):
-        if getattr(self, "_pending_exit_sync", False):
-            torch.cuda.current_stream().wait_stream(SideStreams.get("leg"))
-            self._pending_exit_sync = False
-
     def _exits_batched(self):
         """All exits as one autograd node with batched launches (ExitsFn): the stock L1 loss on
-        stock legs, training-shaped input (no row pitch), no side streams."""
-        return (self.batch_exits and isinstance(self.loss_fn, L1Loss) and not SideStreams.active
-                and PaddedWidth.current is None
+        stock legs, training-shaped input (no row pitch)."""
+        return (self.batch_exits and isinstance(self.loss_fn, L1Loss) and PaddedWidth.current is None
                 and all(isinstance(getattr(self.model, "body_%d" % i).leg, LarvaLeg) for i in range(self.args.num_modules)))
 
     def _all_exits(self, feas, base, truth_tensor):
@@ -476,7 +453,6 @@ class LarvaNet(BaseModel):
             fea = body(fea)
             out, term = self._exit(body.leg, fea, base, truth_tensor)
             terms.append(term)
-        self._sync_exits()
         return mean_of_terms(terms), out
 
     # hipGraph path: one step issues ~330 short kernels; launched one by one from Python the GPU
@@ -497,11 +473,9 @@ class LarvaNet(BaseModel):
         lazy_fwd = self._exits_batched()
         lazy_bwd = (lazy_fwd and self.joint_input_grads and self.defer_wgrad and self._single_consumer_features()
                     and getattr(self, "grad_bucket", None) is not None and self.grad_bucket.intact(self.model))
-        return StepScope(side_streams=self.use_side_streams, defer_wgrad=self.defer_wgrad,
-                         split_flush=self._split_backward(), joint_input_grads=self.joint_input_grads,
-                         seed_grad=1.0 if self.l1_grad_in_forward else None,
-                         dual_chain=self.dual_chain and not self.use_side_streams, lazy_chain_joins=(lazy_fwd, lazy_bwd),
-                         early_loss=early_loss)
+        return StepScope(defer_wgrad=self.defer_wgrad, split_flush=self._split_backward(),
+                         joint_input_grads=self.joint_input_grads, seed_grad=1.0, dual_chain=self.dual_chain,
+                         lazy_chain_joins=(lazy_fwd, lazy_bwd), early_loss=early_loss)
 
     def _single_consumer_features(self):
         """Is every body output read by its exit and the next body only (V2's tail reads them too)?"""

@@ -122,7 +122,6 @@ class LarvaNet(V1.LarvaNet):
                 terms.append(self._exit(body.leg, fea, base, truth_tensor)[1])
         out = net.tail(feats, base)
         terms.append(self.loss_fn(out, truth_tensor))
-        self._sync_exits()
         return mean_of_terms(terms), out
 
     def receptive_halo(self):

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """bench.py's weight-gradient block (one launch over 40 layers + reduction, captured and replayed) at the given channel
-counts, and the partial-image launch alone.  LARVA_WGRAD_PIPE=0 in the environment gives the register-staged kernel of
-every shape, LARVA_HIP_LIB a variant build, for same-box A/Bs.
+counts, and the partial-image launch alone.  LARVA_HIP_LIB in the environment gives a variant build, for same-box A/Bs.
 usage: bench_wgrad_widths.py [C ...]   (default 32 48 64)"""
 import os
 import sys
