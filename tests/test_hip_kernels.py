@@ -881,6 +881,64 @@ def test_flat_wgrad_grid_with_the_head_as_its_tail(hip_device, njobs, nwg, N, H,
     assert all(torch.equal(a, j["dw"]) for a, j in zip(first, jobs + [head]))
 
 
+@pytest.mark.parametrize("njobs,nwg,N,H,W,with_head", [(32, 256, 64, 48, 48, False), (32, 200, 64, 48, 48, False),
+                                                        (8, 256, 16, 96, 96, True)])
+def test_flat_wgrad_grid_with_large_shares(hip_device, njobs, nwg, N, H, W, with_head):
+    """The flat weight-gradient grid at training batches past the headline: a workgroup's share holds 128-164 tiles
+    (32 layers of 64 x 48 x 48 over 256 / 200 workgroups: shares on and across the layer boundaries) or 32+ tiles with
+    the head as the grid's tail (8 layers of 16 x 96 x 96).  Against torch in float64 for the first and the last layer,
+    two layers whose first share starts inside the layer before (where there are such) and the head; run to run the
+    same bits for every layer."""
+    from larvanet_amd import kernels as K
+    gen = torch.Generator(device=hip_device).manual_seed(njobs * 1000 + nwg)
+    jobs = []
+    for _ in range(njobs):
+        jobs.append({"dy": torch.randn(N, 48, H, W, generator=gen, device=hip_device) * 1e-3,
+                     "x": torch.randn(N, 48, H, W, generator=gen, device=hip_device) * 20,
+                     "dw": torch.full((48, 48, 3, 3), float("nan"), device=hip_device),
+                     "db": torch.full((48,), float("nan"), device=hip_device)})
+    head = None
+    if with_head:
+        x16 = torch.zeros(N, 16, H, W, device=hip_device)
+        x16[:, :3] = torch.rand(N, 3, H, W, generator=gen, device=hip_device) * 255
+        head = {"dy": torch.randn(N, 48, H, W, generator=gen, device=hip_device) * 1e-3, "x": x16,
+                "dw": torch.full((48, 3, 3, 3), float("nan"), device=hip_device),
+                "db": torch.full((48,), float("nan"), device=hip_device), "cin_off": 0, "cin_valid": 3}
+
+    def run():
+        parts, splits = K.conv3x3_wgrad_partial_flat(jobs, 48, 48, nwg, head=head)
+        rj = [dict(j, partial=p, splits=s, cout=48, cin=48) for j, p, s in zip(jobs, parts, splits)]
+        if head is not None:
+            rj.append(dict(head, partial=parts[-1], splits=splits[-1], cout=48, cin=16))
+        K.wgrad_reduce(rj)
+        torch.cuda.synchronize()
+        return splits
+
+    splits = run()
+    tiles = N * ((H + 2) // 3) * ((W + 47) // 48)
+    assert len(splits) == njobs + (head is not None)
+    # layers whose first tile is not the first of a share (the share of workgroup w is [G w / nwg, G (w + 1) / nwg));
+    # without the head G is the tile count, with it the head's units lengthen the sequence: check every layer then
+    starts = {njobs * tiles * w // nwg for w in range(nwg)}
+    crossing = [i for i in range(1, njobs) if i * tiles not in starts]
+    check = sorted({0, njobs - 1, *crossing[len(crossing) // 2:len(crossing) // 2 + 2]}) if head is None else range(njobs)
+    if head is None and nwg == 200:
+        assert len(crossing) >= 2 and all(s >= 2 for s in splits)
+    for j, cin_x in [(jobs[i], jobs[i]["x"]) for i in check] + ([(head, head["x"][:, :3])] if head is not None else []):
+        dw_ref = torch.nn.grad.conv2d_weight(cin_x.double().cpu(), tuple(j["dw"].shape), j["dy"].double().cpu(), padding=1)
+        db_ref = j["dy"].double().cpu().sum((0, 2, 3))
+        dw, db = j["dw"].cpu().double(), j["db"].cpu().double()
+        assert float((dw - dw_ref).abs().max()) <= 3e-5 * float(dw_ref.abs().max())
+        assert float((db - db_ref).abs().max()) <= 3e-5 * float(db_ref.abs().max()) + 1e-9
+    every = jobs + ([head] if head is not None else [])
+    first = [j["dw"].clone() for j in every] + [j["db"].clone() for j in every]
+    for j in every:
+        j["dw"].fill_(float("nan"))
+        j["db"].fill_(float("nan"))
+    assert run() == splits
+    assert all(torch.equal(a, b) for a, b in zip(first, [j["dw"] for j in every] + [j["db"] for j in every]))
+
+
 def test_reduce_launch_carries_the_loss_and_adamw_launch_the_copy(hip_device):
     """larva_wgrad_reduce_with_loss == larva_wgrad_reduce + larva_loss_from_partials (same bits), and
     larva_adamw_step_host_copy == larva_adamw_step_host + a 4-byte copy."""
