@@ -265,6 +265,29 @@ int larva_l1_partial_grad_batch(const float* const* a, const float* b, int n, fl
 /* ---- PixelShuffle(4) backward (models/LarvaNet.py:261): in [N][C][4H][4W] -> out [N][16C][H][W] */
 int larva_pixel_unshuffle4(const float* in, float* out, int N, int C, int H, int W, void* stream);
 
+/* ---- x2 / x3 (csrc/larva_scale.hip) ---------------------------------------------------------
+ * A network prepared with scales=[s], s = 2 or 3: the last conv of every leg (and of the V2 tail) has C s^2 outputs
+ * (C = 3: 12 / 27), run as a plain 32-output conv on zero-padded weights; its output / gradient is [N][cpad][H][*]
+ * with cpad >= C s^2, channel c s^2 + i s + j = colour c, sub-pixel (i, j).  Gradient outputs write channels
+ * [C s^2, cpad) as zeros.
+ * F.interpolate(x, scale_factor=scale, mode, align_corners=False), mode 0 bicubic / 1 bilinear, scale 2, 3 or 4 (4 =
+ * larva_upsample4_fwd): in [N][C][H][W] -> out [N][C][scale H][scale W]. */
+int larva_upsample_fwd(const float* in, float* out, int N, int C, int H, int W, int scale, int mode, void* stream);
+/* out [N][C][scale H][scale W] = PixelShuffle(scale)(y) + base (base may be NULL); y [N][cpad][H][pitch] (0 = W). */
+int larva_pixel_shuffle_base(const float* y, const float* base, float* out, int N, int C, int cpad, int H, int W,
+                             int pitch, int scale, void* stream);
+/* PixelShuffle(scale) backward: in [N][C][scale H][scale W] -> out [N][cpad][H][W]. */
+int larva_pixel_unshuffle(const float* in, float* out, int N, int C, int cpad, int H, int W, int scale, void* stream);
+/* L1 backward in that layout: ga [N][cpad][H][W] = sign(a - b) * (gout[0] * gscale) / numel. */
+int larva_l1_bwd_unshuffle(const float* a, const float* b, const float* gout, float gscale, float* ga, int N, int C,
+                           int cpad, int H, int W, int scale, void* stream);
+/* One training exit after its plain conv y [N][cpad][H][W], in one pass: out = PixelShuffle(scale)(y) + base (out may be
+ * NULL), *blocks_out <= larva_l1_workspace_floats() block partial sums of sum|out - truth| into `partial` (for
+ * larva_loss_from_partials, scale 1 / numel) and grad [N][cpad][H][W] = sign(out - truth) * gvalue * gscale / numel. */
+int larva_shuffle_l1_partial_grad(const float* y, const float* base, const float* truth, float gvalue, float gscale,
+                                  float* partial, int* blocks_out, float* grad, float* out, int N, int C, int cpad, int H,
+                                  int W, int scale, void* stream);
+
 /* ---- AdamW over a flat buffer (optim.AdamW, models/LarvaNet.py:86-88,114) ------------------
  * step_lr: device floats {step (1-based), lr}.  g is multiplied by grad_scale first
  * (1/world_size after a sum all-reduce).  Buffers that are all 16-byte aligned are walked 16 bytes per lane

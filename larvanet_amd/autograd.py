@@ -171,10 +171,15 @@ class PackedConv:
     invalidate() is called (restore / load_state_dict / optimizer step do)."""
 
     __slots__ = ("weight", "bias", "cin_pad", "slices", "_key", "_packs", "_bufs", "_prepacked", "grad_inplace",
-                 "joint", "joint_slot")
+                 "joint", "joint_slot", "cout_pad", "_pad")
 
-    def __init__(self, weight, bias, cin_pad=None, slices=None):
+    def __init__(self, weight, bias, cin_pad=None, slices=None, cout_pad=None):
         self.weight, self.bias, self.cin_pad = weight, bias, cin_pad
+        # cout_pad: the conv runs with this many outputs on zero-padded weight rows (the x2 / x3 legs' last conv: 12 / 27
+        # outputs as a 32-output conv).  Persistent padded copies of weight and bias (`_pad`) are refreshed by a
+        # device-to-device copy of the real rows before every pack; the padding rows stay zero.
+        self.cout_pad = cout_pad
+        self._pad = None
         # True once a GradBucket owns weight.grad / bias.grad: the wgrad kernels then write the
         # gradients there directly and the autograd nodes return None for them.
         self.grad_inplace = False
@@ -199,6 +204,9 @@ class PackedConv:
         w = self.weight
         cout, cin_total = int(w.shape[0]), int(w.shape[1])
         dev = w.device
+        if self.cout_pad is not None:
+            w = self._padded(w)
+            cout = self.cout_pad
         if self._bufs is None or self._bufs[0] != (w.data_ptr(), str(dev)):
             def buf(a, b):
                 return torch.empty(K.packed_weight_floats(a, b), device=dev, dtype=torch.float32)
@@ -213,6 +221,22 @@ class PackedConv:
             self._bufs = ((w.data_ptr(), str(dev)), specs)
         wd = w.detach()
         return [(wd, f, b, cout, cin_k, off) for (f, b, cin_k, off) in self._bufs[1]]
+
+    def _padded(self, w):
+        """The padded weight copy, its real rows and the bias refreshed now (on the current stream, in front of the pack
+        launch that reads them; inside a capture they are two copy nodes of the graph)."""
+        rows = int(w.shape[0])
+        if self._pad is None or self._pad[0].device != w.device or tuple(self._pad[0].shape[1:]) != tuple(w.shape[1:]):
+            self._pad = (torch.zeros((self.cout_pad,) + tuple(w.shape[1:]), device=w.device, dtype=torch.float32),
+                         torch.zeros(self.cout_pad, device=w.device, dtype=torch.float32))
+        with torch.no_grad():
+            self._pad[0][:rows].copy_(w.detach())
+            self._pad[1][:rows].copy_(self.bias.detach())
+        return self._pad[0]
+
+    def padded_bias(self):
+        """[cout_pad] bias for the padded conv (valid after the pack that refreshed it)."""
+        return self._pad[1]
 
     def _mark_packed(self):
         self._packs = [(f, b) for (f, b, _, _) in self._bufs[1]]

@@ -1431,6 +1431,8 @@ int larva_conv3x3_wgrad_partial(const float* const* dy, const float* const* x, f
   else if (cout == 64 && cin == 16) e = launch_wgrad<64, 16>(b, njobs, splits, s);
   else if (cout == 48 && cin == 32) e = launch_wgrad<48, 32>(b, njobs, splits, s);
   else if (cout == 48 && cin == 64) e = launch_wgrad<48, 64>(b, njobs, splits, s);
+  // x2 / x3 networks: the legs' last conv, 12 / 27 outputs on 32 zero-padded gradient channels (csrc/larva_scale.hip)
+  else if (cout == 32 && cin == 48) e = launch_wgrad<32, 48>(b, njobs, splits, s);
   else return (int)hipErrorInvalidValue;
   return (int)e;
 }

@@ -506,6 +506,92 @@ def upsample4(x, mode="bicubic"):
     return out
 
 
+def upsample(x, scale, mode="bicubic"):
+    """F.interpolate(x, scale_factor=scale, mode=mode, align_corners=False) for scale 2, 3 or 4 (4 = upsample4)."""
+    if int(scale) == 4:
+        return upsample4(x, mode)
+    lib = hip_lib.load()
+    if mode not in UPSAMPLE_MODES or int(scale) not in (2, 3):
+        raise RuntimeError("larvanet_amd: no kernel for interpolate mode %r at x%s" % (mode, scale))
+    s = int(scale)
+    N, C, H, W = (int(v) for v in x.shape)
+    _chk(x, "x")
+    out = torch.empty((N, C, s * H, s * W), device=x.device, dtype=torch.float32)
+    hip_lib.check(lib.larva_upsample_fwd(x.data_ptr(), out.data_ptr(), N, C, H, W, s, UPSAMPLE_MODES[mode], _stream()),
+                  "larva_upsample_fwd")
+    return out
+
+
+def pixel_shuffle_base(y, base, scale, channels=3, logical_w=None):
+    """x2 / x3 exit image: PixelShuffle(scale)(y[:, :channels * scale**2]) (+ base) for the plain conv output y
+    [N][cpad][H][P] (logical_w: the image is W <= P columns wide) -> [N][channels][scale H][scale W]."""
+    lib = hip_lib.load()
+    s = int(scale)
+    N, cpad, H, P = (int(v) for v in y.shape)
+    W = P if logical_w is None else int(logical_w)
+    _chk(y, "y")
+    hr = (N, channels, s * H, s * W)
+    out = torch.empty(hr, device=y.device, dtype=torch.float32)
+    hip_lib.check(lib.larva_pixel_shuffle_base(y.data_ptr(), _opt(base, "base", hr), out.data_ptr(), N, channels, cpad, H, W,
+                                               P, s, _stream()), "larva_pixel_shuffle_base")
+    return out
+
+
+def _lr_of(hr, scale):
+    N, C, HH, WW = (int(v) for v in hr.shape)
+    if HH % scale or WW % scale:
+        raise RuntimeError("larvanet_amd: spatial dims must be divisible by %d" % scale)
+    return N, C, HH // scale, WW // scale
+
+
+def pixel_unshuffle(g, scale, cpad):
+    """PixelShuffle(scale) backward: [N][C][sH][sW] -> [N][cpad][H][W], channels [C s^2, cpad) zero."""
+    lib = hip_lib.load()
+    s = int(scale)
+    _chk(g, "g")
+    N, C, H, W = _lr_of(g, s)
+    out = torch.empty((N, cpad, H, W), device=g.device, dtype=torch.float32)
+    hip_lib.check(lib.larva_pixel_unshuffle(g.data_ptr(), out.data_ptr(), N, C, cpad, H, W, s, _stream()),
+                  "larva_pixel_unshuffle")
+    return out
+
+
+def l1_bwd_unshuffle(a, b, gout, scale, cpad, gscale=1.0):
+    """Gradient of mean|a - b| * gscale w.r.t. a at scale 2 / 3, written as [N][cpad][H][W] (padding channels zero)."""
+    lib = hip_lib.load()
+    s = int(scale)
+    _chk(a, "a")
+    _chk(b, "b", a.shape)
+    _chk(gout, "gout", ())
+    N, C, H, W = _lr_of(a, s)
+    out = torch.empty((N, cpad, H, W), device=a.device, dtype=torch.float32)
+    hip_lib.check(lib.larva_l1_bwd_unshuffle(a.data_ptr(), b.data_ptr(), gout.data_ptr(), float(gscale), out.data_ptr(),
+                                             N, C, cpad, H, W, s, _stream()), "larva_l1_bwd_unshuffle")
+    return out
+
+
+def shuffle_l1_partial_grad(y, base, truth, gvalue, gscale, scale, want_image=True):
+    """One x2 / x3 training exit after its plain conv y [N][cpad][H][W]: -> (partials, 1 / numel, grad [N][cpad][H][W],
+    image = PixelShuffle(scale)(y) + base or None), the L1 partial sums and the gradient sign(image - truth) * gvalue *
+    gscale / numel from one pass."""
+    lib = hip_lib.load()
+    s = int(scale)
+    _chk(truth, "truth")
+    N, C, H, W = _lr_of(truth, s)
+    cpad = int(y.shape[1])
+    _chk(y, "y", (N, cpad, H, W))
+    _chk(base, "base", truth.shape)
+    part = torch.empty(int(lib.larva_l1_workspace_floats()), device=y.device, dtype=torch.float32)
+    grad = torch.empty((N, cpad, H, W), device=y.device, dtype=torch.float32)
+    out = torch.empty(truth.shape, device=y.device, dtype=torch.float32) if want_image else None
+    blocks = ctypes.c_int(0)
+    hip_lib.check(lib.larva_shuffle_l1_partial_grad(y.data_ptr(), base.data_ptr(), truth.data_ptr(), float(gvalue),
+                                                    float(gscale), part.data_ptr(), ctypes.byref(blocks), grad.data_ptr(),
+                                                    None if out is None else out.data_ptr(), N, C, cpad, H, W, s, _stream()),
+                  "larva_shuffle_l1_partial_grad")
+    return part[:int(blocks.value)], 1.0 / float(truth.numel()), grad, out
+
+
 def bicubic4(x):
     lib = hip_lib.load()
     N, C, H, W = (int(v) for v in x.shape)

@@ -24,6 +24,7 @@ from ..autograd import (BodyFn, DualChain, ExitFn, ExitsFn, GradBucket, HeadFn, 
                         StepScope, is_large_inference, pack_all)
 from ..autograd import step_prologue as autograd_step_prologue
 from ..optim import FlatAdamW, flatten_parameters
+from ..scaled import ScaledExitFn, ScaledLegFn
 from ..metrics import image_psnr, image_to_uint8, fit_truth_image_size
 from .base import BaseModel
 
@@ -40,6 +41,14 @@ NUM_FILTERS = 48  # = 3 * 4**2: PixelShuffle(4) of the leg output must give RGB 
 # conv keeps 48 outputs, so the exits are still RGB.  48 is the reference's network, bit for bit; other widths have no
 # reference counterpart and are checked against oracle/larva_torch.py only.
 SUPPORTED_NUM_FILTERS = (32, 48, 64)
+# prepare(scales=[s]), s = 2 / 3: the legs' last conv has 3 * s**2 = 12 / 27 outputs (PixelShuffle(s) gives RGB) and runs
+# as a 32-output conv on zero-padded weight rows (larvanet_amd/scaled.py).  Those ends exist for the reference's width
+# only: --num_filters 32 / 64 at x2 / x3 is refused by prepare().
+SCALED_COUT_PAD = 32
+
+
+def leg_outputs(scale):
+    return 3 * scale * scale
 
 
 def create_model():
@@ -113,31 +122,37 @@ class LarvaHead(nn.Module):
 class LarvaLeg(nn.Module):
     """models/LarvaNet.py:251-267"""
 
-    def __init__(self, num_filters=NUM_FILTERS):
+    def __init__(self, num_filters=NUM_FILTERS, scale=4):
         super().__init__()
+        self.scale = scale
+        # 3 * scale**2 outputs whatever the width: 48 at x4, 12 / 27 at x2 / x3
         self.recon_block = nn.Sequential(_conv(num_filters, num_filters), nn.ReLU(inplace=True),
-                                         _conv(num_filters, NUM_FILTERS))   # 48 = 3 * 4**2 outputs whatever the width
+                                         _conv(num_filters, leg_outputs(scale)))
         init_conv(self.recon_block[0])
         init_conv(self.recon_block[2])
-        self.upsample = nn.PixelShuffle(4)  # kept for introspection; fused into the conv store
+        self.upsample = nn.PixelShuffle(scale)  # kept for introspection; fused into the conv store / the shuffle kernel
         self._pcs = [PackedConv(self.recon_block[0].weight, self.recon_block[0].bias),
-                     PackedConv(self.recon_block[2].weight, self.recon_block[2].bias)]
+                     PackedConv(self.recon_block[2].weight, self.recon_block[2].bias,
+                                cout_pad=None if scale == 4 else SCALED_COUT_PAD)]
 
     def forward(self, fea, base):
         _require_hip(fea)
         c1, c2 = self.recon_block[0], self.recon_block[2]
         for pc in self._pcs:
             pc.refresh()
+        if self.scale != 4:
+            return ScaledLegFn.apply(fea.contiguous(), base.contiguous(), self._pcs, self.scale, c1.weight, c1.bias,
+                                     c2.weight, c2.bias)
         return LegFn.apply(fea.contiguous(), base.contiguous(), self._pcs, c1.weight, c1.bias, c2.weight, c2.bias)
 
 
 class LarvaBody(nn.Module):
     """models/LarvaNet.py:236-248"""
 
-    def __init__(self, num_blocks, num_filters=NUM_FILTERS):
+    def __init__(self, num_blocks, num_filters=NUM_FILTERS, scale=4):
         super().__init__()
         self.res_blocks = nn.Sequential(*[ResidualBlock(num_filters) for _ in range(num_blocks)])
-        self.leg = LarvaLeg(num_filters)
+        self.leg = LarvaLeg(num_filters, scale)
         self._pcs = []
         for blk in self.res_blocks:
             self._pcs += [PackedConv(blk.body[0].weight, blk.body[0].bias),
@@ -176,9 +191,10 @@ class LarvaNetModule(nn.Module):
         self.num_filters = int(getattr(args, "num_filters", NUM_FILTERS))
         if self.num_filters not in SUPPORTED_NUM_FILTERS:
             raise ValueError("larvanet_amd: --num_filters must be one of %s" % (SUPPORTED_NUM_FILTERS,))
+        self.scale = int(getattr(args, "scale", 4))   # (set by prepare())
         self.head = LarvaHead(self.num_filters)
         for i, nb in enumerate(parse_num_blocks(args)):
-            setattr(self, "body_%d" % i, LarvaBody(num_blocks=nb, num_filters=self.num_filters))
+            setattr(self, "body_%d" % i, LarvaBody(num_blocks=nb, num_filters=self.num_filters, scale=self.scale))
         self._join_input_grads()
 
     def _join_input_grads(self):
@@ -209,20 +225,21 @@ class LarvaNetModule(nn.Module):
         """refresh_packed_weights() + base(x) + the head's padded input as ONE launch -> (base, x16);
         x16 is None when the fused launch does not apply (the head then pads its input itself)."""
         _require_hip(x)
-        res = autograd_step_prologue(self.packed_convs(), x) if self.interpolate == "bicubic" else None
+        # (the fused launch computes the x4 base image)
+        res = autograd_step_prologue(self.packed_convs(), x) if self.interpolate == "bicubic" and self.scale == 4 else None
         if res is None:
             self.refresh_packed_weights()
             return self.base(x), None
         return res[1], res[0]
 
     def base(self, x):
-        """F.interpolate(x, scale_factor=4, mode=args.interpolate, align_corners=False) (models/LarvaNet.py:283-285)."""
+        """F.interpolate(x, scale_factor=scale, mode=args.interpolate, align_corners=False) (models/LarvaNet.py:283-285)."""
         _require_hip(x)
         if self.interpolate not in SUPPORTED_INTERPOLATE:   # (parse_args already refuses it)
             raise ValueError("larvanet_amd: --interpolate=%s has no HIP kernel; supported: %s"
                              % (self.interpolate, ", ".join(SUPPORTED_INTERPOLATE)))
         with torch.no_grad():
-            return K.upsample4(x.detach().contiguous(), self.interpolate)
+            return K.upsample(x.detach().contiguous(), self.scale, self.interpolate)
 
     def width_scope(self, x):
         """Row-padded activations for inference on widths that are not a multiple of 4."""
@@ -326,10 +343,16 @@ class LarvaNet(BaseModel):
         if len(self.scale_list) != 1:
             raise ValueError("Only one scale should be provided.")
         self.scale = self.scale_list[0]
+        nf = int(getattr(self.args, "num_filters", NUM_FILTERS))
+        if self.scale != 4 and nf != NUM_FILTERS:
+            raise ValueError("larvanet_amd: --num_filters %d at x%d is not supported (x2 / x3 networks are built at "
+                             "--num_filters %d only)" % (nf, self.scale, NUM_FILTERS))
 
         self.device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() \
             else torch.device("cpu")
-        self.model = self.module_class(args=self.args).to(self.device)
+        margs = copy.copy(self.args)
+        margs.scale = self.scale
+        self.model = self.module_class(args=margs).to(self.device)
         ldist.broadcast_parameters(self.model)  # no-op unless torch.distributed is initialised
 
         if is_training:
@@ -400,6 +423,13 @@ class LarvaNet(BaseModel):
         the stock L1Loss; otherwise the two separate calls of the reference.  Returns (image, term):
         in the fused case the term is a LossTerm of partial sums that the mean over the exits
         finishes (no per-exit finishing launch, the 1/M of the mean applied inside L1's backward)."""
+        if isinstance(self.loss_fn, L1Loss) and isinstance(leg, LarvaLeg) and leg.scale != 4:
+            for pc in leg._pcs:
+                pc.refresh()
+            c1, c2 = leg.recon_block[0], leg.recon_block[2]
+            out, part = ScaledExitFn.apply(fea.contiguous(), base.contiguous(), truth_tensor.contiguous(), leg._pcs, leg.scale,
+                                           self._num_loss_terms(), c1.weight, c1.bias, c2.weight, c2.bias)
+            return out, LossTerm(part, 1.0 / float(out.numel()), prescaled=True)
         if isinstance(self.loss_fn, L1Loss) and isinstance(leg, LarvaLeg):
             for pc in leg._pcs:
                 pc.refresh()
@@ -414,6 +444,7 @@ class LarvaNet(BaseModel):
         """All exits as one autograd node with batched launches (ExitsFn): the stock L1 loss on
         stock legs, training-shaped input (no row pitch)."""
         return (self.batch_exits and isinstance(self.loss_fn, L1Loss) and PaddedWidth.current is None
+                and self.model.scale == 4   # (x2 / x3: one ScaledExitFn per exit)
                 and all(isinstance(getattr(self.model, "body_%d" % i).leg, LarvaLeg) for i in range(self.args.num_modules)))
 
     def _all_exits(self, feas, base, truth_tensor):
@@ -684,6 +715,12 @@ class LarvaNet(BaseModel):
         return ev
 
     def train_step_larva(self, args, val_dataloader, input_tensor, truth_tensor, summary=None):
+        n, c, h, w = (int(v) for v in input_tensor.shape)
+        s = self.model.scale
+        if tuple(truth_tensor.shape) != (n, c, s * h, s * w):
+            # (the kernels would read the truth as if it had this shape)
+            raise ValueError("larvanet_amd: truth of shape %s for an input of %s at x%d; expected %s"
+                             % (tuple(truth_tensor.shape), tuple(input_tensor.shape), s, (n, c, s * h, s * w)))
         self.global_step += 1
         self.temp_volume += self.volume_per_step
 
@@ -773,7 +810,7 @@ class LarvaNet(BaseModel):
         psnr_sum = 0.0
         with torch.no_grad():
             for image_index in range(ldist.rank(), num_images, ldist.world_size()):
-                input_image, truth_image, _ = dataloader.get_image_pair(image_index=image_index, scale=4)
+                input_image, truth_image, _ = dataloader.get_image_pair(image_index=image_index, scale=self.scale)
                 psnr_sum += self.image_psnr(input_image, truth_image)
         average_psnr = ldist.allreduce_scalar_sum(psnr_sum, self.device) / max(num_images, 1)
         print(f"step {self.global_step}, volume {self.total_volume/1e9:.0f}G,"
@@ -789,7 +826,7 @@ class LarvaNet(BaseModel):
             out = self.model(self._to_input_tensor([input_image]))[0].contiguous()
             truth8 = torch.from_numpy(np.ascontiguousarray(image_to_uint8(truth_image))).to(self.device)
             return K.psnr_u8(out, truth8)
-        output_image = image_to_uint8(self.upscale(input_list=[input_image], scale=4)[0])
+        output_image = image_to_uint8(self.upscale(input_list=[input_image], scale=self.scale)[0])
         truth8 = fit_truth_image_size(output_image=output_image, truth_image=image_to_uint8(truth_image))
         return float(image_psnr(output_image=output_image, truth_image=truth8))
 

@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from ..autograd import DualChain, LegFn, MergeFn, PackedConv, mean_of_terms
+from ..scaled import ScaledLegFn
 from . import LarvaNet as V1
 from .LarvaNet import NUM_FILTERS, _conv, _require_hip, init_conv
 
@@ -23,20 +24,22 @@ def create_model():
 class LarvaTail(nn.Module):
     """models/LarvaNetV2.py:314-334"""
 
-    def __init__(self, num_modules, num_filters=NUM_FILTERS):
+    def __init__(self, num_modules, num_filters=NUM_FILTERS, scale=4):
         super().__init__()
+        self.scale = scale
         self.merge_conv = _conv(num_filters * num_modules, num_filters)
         self.recon_block = nn.Sequential(_conv(num_filters, num_filters), nn.ReLU(inplace=True),
-                                         _conv(num_filters, NUM_FILTERS))
+                                         _conv(num_filters, V1.leg_outputs(scale)))
         # the reference initialises [recon_block, merge_conv] in that order (:324)
         init_conv(self.recon_block[0])
         init_conv(self.recon_block[2])
         init_conv(self.merge_conv)
-        self.upsample = nn.PixelShuffle(4)
+        self.upsample = nn.PixelShuffle(scale)
         self._pc = PackedConv(self.merge_conv.weight, self.merge_conv.bias,
                               slices=[(i * num_filters, num_filters) for i in range(num_modules)])
         self._pcs = [PackedConv(self.recon_block[0].weight, self.recon_block[0].bias),
-                     PackedConv(self.recon_block[2].weight, self.recon_block[2].bias)]
+                     PackedConv(self.recon_block[2].weight, self.recon_block[2].bias,
+                                cout_pad=None if scale == 4 else V1.SCALED_COUT_PAD)]
 
     def forward(self, features, base):
         _require_hip(features[0])
@@ -46,6 +49,8 @@ class LarvaTail(nn.Module):
         m = self.merge_conv
         fea = MergeFn.apply(self._pc, m.weight, m.bias, *[f.contiguous() for f in features])
         c1, c2 = self.recon_block[0], self.recon_block[2]
+        if self.scale != 4:
+            return ScaledLegFn.apply(fea, base.contiguous(), self._pcs, self.scale, c1.weight, c1.bias, c2.weight, c2.bias)
         return LegFn.apply(fea, base.contiguous(), self._pcs, c1.weight, c1.bias, c2.weight, c2.bias)
 
 
@@ -54,7 +59,7 @@ class LarvaNetModule(V1.LarvaNetModule):
 
     def __init__(self, args):
         super().__init__(args)
-        self.tail = LarvaTail(self.len, self.num_filters)
+        self.tail = LarvaTail(self.len, self.num_filters, self.scale)
 
     def features(self, x):
         fea = self.head(x)
