@@ -13,6 +13,8 @@
 #ifndef LARVA_HIP_H
 #define LARVA_HIP_H
 
+#include <stdint.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -323,6 +325,36 @@ int larva_gather_patches(const unsigned char* data, const long long* offsets, co
  * [C][TH][TW] uint8 cropped top-left; exact integer.  Caller zeroes acc. */
 int larva_sqerr_u8(const float* out, const unsigned char* truth, int C, int H, int W, int TH, int TW,
                    unsigned long long* acc, void* stream);
+
+/* ---- fp16 inference (--precision fp16; csrc/conv3x3_f16.hip) -------------------------------------
+ * Grad-free x4 forward at 48 channels on v_mfma_f32_16x16x32_f16: fp16 storage, fp32 accumulation.  fp16 tensors are
+ * uint16_t bit images of IEEE half, CHANNELS-LAST [N][H][W][48] (not the fp32 NCHW of the entry points above); images
+ * and bases stay fp32 NCHW.  `flag` is one device unsigned that an fp16-storing launch sets to 1 (never clears) when a
+ * value is not finite or exceeds 65504 in magnitude before it is rounded; the caller zeroes it.
+ *
+ * larva_f16_packed_weight_halves(48, 48 m) = m * 14 * 3 * 64 * 8 (m <= 8; -1 for any other shape): the A-operand image of
+ * a [48][48 m][3][3] fp32 weight, [src m][K-step 14][M tile 3][lane 64][8] halves, K = (tap, 8-channel group), rounded to
+ * nearest even; larva_f16_pack_weights writes it in one launch. */
+long long larva_f16_packed_weight_halves(int cout, int cin);
+int larva_f16_pack_weights(const float* w, uint16_t* wpk, int cout, int cin, void* stream);
+
+/* Head conv (models/LarvaNet.py:227): x fp32 [N][3][H][W] -> out fp16 [N][H][W][48] = conv(x, w) + bias, w the fp32
+ * [48][3][3][3] parameter itself.  fp32 operands and an fp32 fmaf chain (VALU), then one rounding to fp16. */
+int larva_f16_head(const float* x, const float* w, const float* bias, uint16_t* out, unsigned* flag, int N, int H,
+                   int W, void* stream);
+
+/* 48 -> 48 conv over nsrc (1..8) fp16 inputs read as consecutive 48-channel K chunks (the V2 merge conv over the body
+ * outputs without a concatenation, models/LarvaNetV2.py:330), wpk packed for cin = 48 nsrc.  Epilogue in fp32:
+ * + bias, then ReLU (relu != 0; models/LarvaNet.py:210-212,256) or + res0 (+ res1: the body's outer skip,
+ * models/LarvaNet.py:219,247), rounded once to fp16.  relu excludes res0; res1 needs res0.  srcs is a host array. */
+int larva_f16_conv3x3(const uint16_t* const* srcs, int nsrc, const uint16_t* wpk, const float* bias,
+                      const uint16_t* res0, const uint16_t* res1, int relu, uint16_t* out, unsigned* flag, int N, int H,
+                      int W, void* stream);
+
+/* Leg end (models/LarvaNet.py:258-265): out fp32 [N][3][4H][4W] = PixelShuffle(4)(conv(src) + bias) + base, base the
+ * fp32 x4 base image (larva_upsample4_fwd). */
+int larva_f16_conv3x3_shuffle_base(const uint16_t* src, const uint16_t* wpk, const float* bias, const float* base,
+                                   float* out, int N, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,134 @@
+"""fp16 inference forward (--precision fp16): the grad-free x4 network at 48 filters on the f16-MFMA kernels of
+csrc/conv3x3_f16.hip, over the parameters of the existing module tree (head, bodies, the legs or the V2 tail).
+
+Activations are fp16 channels-last [N][H][W][48]; every conv accumulates in fp32 and rounds its epilogue's result
+(bias, ReLU, residual adds) once to fp16.  The image going in and the HR image coming out are fp32 NCHW, and the base
+image is the fp32 path's own bicubic / bilinear kernel, so only the internal activations change precision.  Training,
+validate_for_train and every grad-enabled call stay on the fp32 path (the plugins only dispatch here without
+gradients).
+
+Every fp16-storing launch sets a device flag when a value leaves the fp16 range (or is not finite); the flag is sticky
+until read (take_overflow)."""
+import torch
+
+from . import kernels as K
+
+
+class HalfPack:
+    """fp16 A-operand image of one conv weight in a persistent buffer, repacked by one launch when the weight's storage
+    or version moves or after invalidate() -- PackedConv's staleness rules for inference.  The buffer keeps its address,
+    so a captured graph that reads it sees the repacked image."""
+
+    __slots__ = ("weight", "_key", "_buf")
+
+    def __init__(self, weight):
+        self.weight = weight
+        self._key = None
+        self._buf = None
+
+    def invalidate(self):
+        self._key = None
+
+    def get(self):
+        w = self.weight
+        key = (w.data_ptr(), w._version, str(w.device))
+        if key != self._key:
+            buf = self._buf if self._buf is not None and self._buf.device == w.device else None
+            self._buf = K.f16_pack_weights(w.detach(), out=buf)
+            self._key = key
+        return self._buf
+
+
+class HalfForward:
+    """The fp16 forward of one LarvaNetModule (V1, V2, LarvaLeg, LarvaLegV2)."""
+
+    def __init__(self, net):
+        self.net = net
+        self._packs = {}
+        self._flag = None
+
+    def _convs(self):
+        net = self.net
+        legs = getattr(net, "leg", None)
+        nb = net.len if legs is None else legs
+        out = []
+        for i in range(nb):
+            body = getattr(net, "body_%d" % i)
+            for blk in body.res_blocks:
+                out += [blk.body[0], blk.body[2]]
+        if legs is None and hasattr(net, "tail"):
+            out += [net.tail.merge_conv, net.tail.recon_block[0], net.tail.recon_block[2]]
+        elif nb > 0:
+            rb = getattr(net, "body_%d" % (nb - 1)).leg.recon_block
+            out += [rb[0], rb[2]]
+        return out
+
+    def _wpk(self, conv):
+        p = self._packs.get(id(conv))
+        if p is None or p.weight is not conv.weight:
+            p = self._packs[id(conv)] = HalfPack(conv.weight)
+        return p.get()
+
+    def refresh(self):
+        """Repack the stale weight images now (outside a graph, before a replay reads them)."""
+        for c in self._convs():
+            self._wpk(c)
+
+    def invalidate(self):
+        for p in self._packs.values():
+            p.invalidate()
+
+    def flag(self, device):
+        if self._flag is None or self._flag.device != device:
+            self._flag = torch.zeros(1, device=device, dtype=torch.int32)
+        return self._flag
+
+    def clear_overflow(self):
+        if self._flag is not None:
+            self._flag.zero_()
+
+    def take_overflow(self):
+        """True if an fp16 launch overflowed since the last call (host sync); clears the flag."""
+        if self._flag is None:
+            return False
+        hit = bool(int(self._flag.item()))
+        if hit:
+            self._flag.zero_()
+        return hit
+
+    def _conv(self, conv, srcs, flag, **epi):
+        return K.f16_conv3x3(srcs, self._wpk(conv), conv.bias.detach(), flag, **epi)
+
+    def _body(self, body, x, flag):
+        blocks = list(body.res_blocks)
+        fea = x
+        for j, blk in enumerate(blocks):
+            h = self._conv(blk.body[0], fea, flag, relu=True)
+            # the last block's second conv also adds the body's outer skip (models/LarvaNet.py:247)
+            fea = self._conv(blk.body[2], h, flag, res0=fea, res1=x if j == len(blocks) - 1 else None)
+        return fea
+
+    def _leg_end(self, recon_block, fea, base, flag):
+        c1, c2 = recon_block[0], recon_block[2]
+        h = self._conv(c1, fea, flag, relu=True)
+        return K.f16_conv3x3_shuffle_base(h, self._wpk(c2), c2.bias.detach(), base)
+
+    def __call__(self, x):
+        net = self.net
+        x = x.contiguous()
+        base = net.base(x)
+        legs = getattr(net, "leg", None)
+        if legs == 0:
+            return base
+        flag = self.flag(x.device)
+        head = net.head.feature_extraction
+        fea = K.f16_head(x, head.weight.detach(), head.bias.detach(), flag)
+        nb = net.len if legs is None else legs
+        feats = []
+        for i in range(nb):
+            fea = self._body(getattr(net, "body_%d" % i), fea, flag)
+            feats.append(fea)
+        if legs is None and hasattr(net, "tail"):
+            fea = self._conv(net.tail.merge_conv, feats, flag)
+            return self._leg_end(net.tail.recon_block, fea, base, flag)
+        return self._leg_end(getattr(net, "body_%d" % (nb - 1)).leg.recon_block, fea, base, flag)

@@ -129,6 +129,15 @@ SIGNATURES = {
     "larva_adamw_step": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p,
                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                         ctypes.c_float, ctypes.c_longlong, ctypes.c_void_p]),
+    "larva_f16_packed_weight_halves": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
+    "larva_f16_pack_weights": (ctypes.c_int, [_c_float_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "larva_f16_head": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                      ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "larva_f16_conv3x3": (ctypes.c_int, [_c_pp, ctypes.c_int, ctypes.c_void_p, _c_float_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_void_p]),
+    "larva_f16_conv3x3_shuffle_base": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p, _c_float_p,
+                                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
 }
 
 _lib = None

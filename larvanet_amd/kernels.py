@@ -863,3 +863,111 @@ def psnr_u8(out_chw, truth_u8):
     sq = int(acc.item())
     mse = sq / float(C * H * W)
     return float("inf") if mse == 0 else 10.0 * math.log10(255.0 ** 2 / mse)
+
+
+# ------------------------------------------------------------------ fp16 inference (csrc/conv3x3_f16.hip)
+F16_CHANNELS = 48
+F16_MAX_SOURCES = 8
+
+
+def _chk16(t, name, shape=None):
+    """An fp16 channels-last activation [N][H][W][48] (torch.float16, contiguous, on the device)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("larvanet_amd: %s must be a tensor on a HIP device (no CPU path exists)" % name)
+    if t.dtype != torch.float16 or not t.is_contiguous():
+        raise RuntimeError("larvanet_amd: %s must be a contiguous float16 tensor, got %s" % (name, t.dtype))
+    if t.dim() != 4 or int(t.shape[3]) != F16_CHANNELS:
+        raise RuntimeError("larvanet_amd: %s must be [N][H][W][%d], got %s" % (name, F16_CHANNELS, tuple(t.shape)))
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise RuntimeError("larvanet_amd: %s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
+    return t.data_ptr()
+
+
+def _chk_flag(flag):
+    if not isinstance(flag, torch.Tensor) or not flag.is_cuda or flag.dtype != torch.int32 or flag.numel() < 1:
+        raise RuntimeError("larvanet_amd: the overflow flag must be an int32 device tensor")
+    return flag.data_ptr()
+
+
+def f16_packed_weight_halves(cout, cin):
+    return int(hip_lib.load().larva_f16_packed_weight_halves(cout, cin))
+
+
+def f16_pack_weights(w, out=None):
+    """[48][48 m][3][3] fp32 weight -> its fp16 A-operand image (flat float16 tensor, include/larva_hip.h)."""
+    lib = hip_lib.load()
+    _chk(w, "w")
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+        raise RuntimeError("larvanet_amd: only [cout][cin][3][3] weights are supported")
+    cout, cin = int(w.shape[0]), int(w.shape[1])
+    n = f16_packed_weight_halves(cout, cin)
+    if n < 0:
+        raise RuntimeError("larvanet_amd: no fp16 conv for %d -> %d channels" % (cin, cout))
+    if out is None:
+        out = torch.empty(n, device=w.device, dtype=torch.float16)
+    if out.dtype != torch.float16 or out.numel() != n or not out.is_contiguous():
+        raise RuntimeError("larvanet_amd: fp16 weight image must be %d contiguous halves" % n)
+    hip_lib.check(lib.larva_f16_pack_weights(w.data_ptr(), out.data_ptr(), cout, cin, _stream()), "larva_f16_pack_weights")
+    return out
+
+
+def f16_head(x, w, bias, flag, out=None):
+    """x fp32 [N][3][H][W] -> fp16 [N][H][W][48] = conv(x, w) + bias (fp32 operands, one rounding to fp16)."""
+    lib = hip_lib.load()
+    N, C, H, W = (int(v) for v in x.shape)
+    _chk(x, "x")
+    _chk(w, "w", (F16_CHANNELS, 3, 3, 3))
+    _chk(bias, "bias", (F16_CHANNELS,))
+    if C != 3:
+        raise RuntimeError("larvanet_amd: the fp16 head takes 3-channel images")
+    if out is None:
+        out = torch.empty((N, H, W, F16_CHANNELS), device=x.device, dtype=torch.float16)
+    _chk16(out, "out", (N, H, W, F16_CHANNELS))
+    hip_lib.check(lib.larva_f16_head(x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), _chk_flag(flag), N, H, W,
+                                     _stream()), "larva_f16_head")
+    return out
+
+
+def f16_conv3x3(srcs, wpk, bias, flag, relu=False, res0=None, res1=None, out=None):
+    """48 -> 48 conv over the fp16 tensors `srcs` (consecutive 48-channel K chunks), + bias, then ReLU or + res0
+    (+ res1), rounded once to fp16 -> [N][H][W][48]."""
+    lib = hip_lib.load()
+    if isinstance(srcs, torch.Tensor):
+        srcs = [srcs]
+    if not 1 <= len(srcs) <= F16_MAX_SOURCES:
+        raise RuntimeError("larvanet_amd: the fp16 conv takes 1 to %d inputs" % F16_MAX_SOURCES)
+    shape = tuple(srcs[0].shape)
+    ptrs = [_chk16(s, "srcs[%d]" % i, shape) for i, s in enumerate(srcs)]
+    N, H, W = shape[:3]
+    if wpk.dtype != torch.float16 or not wpk.is_cuda or wpk.numel() != f16_packed_weight_halves(F16_CHANNELS, F16_CHANNELS * len(srcs)):
+        raise RuntimeError("larvanet_amd: wpk is not the fp16 image of a %d-input conv" % len(srcs))
+    _chk(bias, "bias", (F16_CHANNELS,))
+    if relu and res0 is not None:
+        raise RuntimeError("larvanet_amd: the fp16 conv has no ReLU + residual epilogue")
+    if res1 is not None and res0 is None:
+        raise RuntimeError("larvanet_amd: res1 needs res0")
+    r0 = None if res0 is None else _chk16(res0, "res0", shape)
+    r1 = None if res1 is None else _chk16(res1, "res1", shape)
+    if out is None:
+        out = torch.empty(shape, device=srcs[0].device, dtype=torch.float16)
+    _chk16(out, "out", shape)
+    hip_lib.check(lib.larva_f16_conv3x3(hip_lib.ptr_array(ptrs), len(ptrs), wpk.data_ptr(), bias.data_ptr(), r0, r1,
+                                        int(bool(relu)), out.data_ptr(), _chk_flag(flag), N, H, W, _stream()),
+                  "larva_f16_conv3x3")
+    return out
+
+
+def f16_conv3x3_shuffle_base(src, wpk, bias, base):
+    """Leg end: fp32 [N][3][4H][4W] = PixelShuffle(4)(conv(src) + bias) + base, src fp16 [N][H][W][48]."""
+    lib = hip_lib.load()
+    _chk16(src, "src")
+    N, H, W = (int(v) for v in src.shape[:3])
+    if wpk.dtype != torch.float16 or not wpk.is_cuda or wpk.numel() != f16_packed_weight_halves(F16_CHANNELS, F16_CHANNELS):
+        raise RuntimeError("larvanet_amd: wpk is not the fp16 image of a 48 -> 48 conv")
+    _chk(bias, "bias", (F16_CHANNELS,))
+    hr = (N, 3, 4 * H, 4 * W)
+    _chk(base, "base", hr)
+    out = torch.empty(hr, device=src.device, dtype=torch.float32)
+    hip_lib.check(lib.larva_f16_conv3x3_shuffle_base(src.data_ptr(), wpk.data_ptr(), bias.data_ptr(), base.data_ptr(),
+                                                     out.data_ptr(), N, H, W, _stream()), "larva_f16_conv3x3_shuffle_base")
+    return out

@@ -45,6 +45,10 @@ SUPPORTED_NUM_FILTERS = (32, 48, 64)
 # as a 32-output conv on zero-padded weight rows (larvanet_amd/scaled.py).  Those ends exist for the reference's width
 # only: --num_filters 32 / 64 at x2 / x3 is refused by prepare().
 SCALED_COUT_PAD = 32
+# --precision (build-side extension): fp16 runs the grad-free inference entry points (upscale, upscale_tensor, test,
+# fwd_runtime) on fp16 activations with fp32 accumulation (larvanet_amd/half.py); training and every grad-enabled call
+# stay fp32.  fp16 exists for the reference's network at x4 only: other scales / widths are refused by prepare().
+SUPPORTED_PRECISIONS = ("fp32", "fp16")
 
 
 def leg_outputs(scale):
@@ -192,6 +196,7 @@ class LarvaNetModule(nn.Module):
         if self.num_filters not in SUPPORTED_NUM_FILTERS:
             raise ValueError("larvanet_amd: --num_filters must be one of %s" % (SUPPORTED_NUM_FILTERS,))
         self.scale = int(getattr(args, "scale", 4))   # (set by prepare())
+        self._half = None   # half.HalfForward, built at the first fp16 inference
         self.head = LarvaHead(self.num_filters)
         for i, nb in enumerate(parse_num_blocks(args)):
             setattr(self, "body_%d" % i, LarvaBody(num_blocks=nb, num_filters=self.num_filters, scale=self.scale))
@@ -216,6 +221,15 @@ class LarvaNetModule(nn.Module):
         """Forget the kernel-layout weight images (call after changing weights behind torch's back)."""
         for pc in self.packed_convs():
             pc.invalidate()
+        if self._half is not None:
+            self._half.invalidate()
+
+    def half_forward(self):
+        """The fp16 inference forward over this module's parameters (--precision fp16)."""
+        if self._half is None:
+            from ..half import HalfForward
+            self._half = HalfForward(self)
+        return self._half
 
     def refresh_packed_weights(self):
         """Rebuild every conv's kernel-layout image with one batched launch (training forward)."""
@@ -315,6 +329,10 @@ class LarvaNet(BaseModel):
         parser.add_argument("--num_filters", type=int, default=NUM_FILTERS, choices=SUPPORTED_NUM_FILTERS,
                             help="Channels of the head / bodies / legs (the legs' last conv keeps 48). "
                                  "The reference hard-wires 48.")
+        parser.add_argument("--precision", type=str, default="fp32", choices=SUPPORTED_PRECISIONS,
+                            help="Activation precision of inference (upscale / test / fwd_runtime): fp16 stores "
+                                 "activations in fp16 and accumulates in fp32 (x4, --num_filters 48 only). "
+                                 "Training is always fp32.")
 
     def parse_args(self, args):
         parser = argparse.ArgumentParser()
@@ -347,6 +365,14 @@ class LarvaNet(BaseModel):
         if self.scale != 4 and nf != NUM_FILTERS:
             raise ValueError("larvanet_amd: --num_filters %d at x%d is not supported (x2 / x3 networks are built at "
                              "--num_filters %d only)" % (nf, self.scale, NUM_FILTERS))
+        self.precision = getattr(self.args, "precision", "fp32")
+        if self.precision not in SUPPORTED_PRECISIONS:
+            raise ValueError("larvanet_amd: --precision must be one of %s" % (SUPPORTED_PRECISIONS,))
+        if self.precision == "fp16" and (self.scale != 4 or nf != NUM_FILTERS):
+            raise ValueError("larvanet_amd: --precision fp16 is built for x4 at --num_filters %d only (got x%d, "
+                             "--num_filters %d)" % (NUM_FILTERS, self.scale, nf))
+        if self.precision == "fp16" and min(parse_num_blocks(self.args)) < 1:
+            raise ValueError("larvanet_amd: --precision fp16 needs at least one residual block per body")
 
         self.device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() \
             else torch.device("cpu")
@@ -843,30 +869,36 @@ class LarvaNet(BaseModel):
         validation images all differ in size -- run eagerly.  The returned tensor of a replay is the
         graph's output buffer: callers that keep it across calls copy it (upscale() moves it to the
         host anyway)."""
-        if not (self.use_hip_graph and x.is_cuda) or torch.is_grad_enabled():
+        if torch.is_grad_enabled():
             return self.model(x)
+        if not (self.use_hip_graph and x.is_cuda):
+            return self._forward_nograd(x)
         # A whole validation image is 36 launches of 60 us each: the host is ~2 ms ahead of the GPU after the first few,
         # and eager launches have no replay boundary and no copy into a static input: 2.162 against 2.178 ms per
         # 339 x 510 image (tools/infer_modes.py, round 5).  The capture pays where the launches are short.
         if is_large_inference(x.shape[0], x.shape[2], x.shape[3]):   # (the same rule picks the direct head kernel)
-            return self.model(x)
+            return self._forward_nograd(x)
         cache = self.__dict__.setdefault("_infer_graphs", {})
         seen = self.__dict__.setdefault("_infer_seen", {})
-        key = tuple(x.shape)
+        key = (tuple(x.shape), self._precision())
         ent = cache.get(key)
         if ent is None:
             if len(seen) > 512:   # (a long run over images of ever new sizes: forget the counts)
                 seen.clear()
             seen[key] = seen.get(key, 0) + 1
             if seen[key] < 2 or len(cache) >= 4:
-                return self.model(x)
+                return self._forward_nograd(x)
             ent = cache[key] = self._capture_infer(x)
             if ent is False:
-                return self.model(x)
+                return self._forward_nograd(x)
         if ent is False:
-            return self.model(x)
-        for pc in self.model.packed_convs():   # weights restored / stepped since the capture: repack (outside the graph)
-            pc.refresh()
+            return self._forward_nograd(x)
+        # weights restored / stepped since the capture: repack (outside the graph)
+        if self._precision() == "fp16":
+            self.model.half_forward().refresh()
+        else:
+            for pc in self.model.packed_convs():
+                pc.refresh()
         static_x, graph, out = ent
         static_x.copy_(x)
         graph.replay()
@@ -880,12 +912,12 @@ class LarvaNet(BaseModel):
             with torch.cuda.stream(side):
                 for _ in range(2):
                     with self._infer_scope():
-                        self.model(static_x)
+                        self._forward_nograd(static_x)
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
                 with self._infer_scope():
-                    out = self.model(static_x)
+                    out = self._forward_nograd(static_x)
             return static_x, graph, out
         except Exception as e:   # an optimisation only
             if self.strict_graph:
@@ -895,6 +927,36 @@ class LarvaNet(BaseModel):
             torch.cuda.synchronize()
             return False
 
+    def _precision(self):
+        return getattr(self, "precision", "fp32")
+
+    def _forward_nograd(self, x):
+        """The inference forward at the model's precision (no graph)."""
+        if self._precision() == "fp16":
+            return self.model.half_forward()(x)
+        return self.model(x)
+
+    def _clear_overflow(self):
+        if self._precision() == "fp16":
+            self.model.half_forward().clear_overflow()
+
+    def _check_overflow(self):
+        """upscale / upscale_tensor / test: an fp16 activation that left the fp16 range is an error, not a result."""
+        if self._precision() == "fp16" and self.model.half_forward().take_overflow():
+            raise FloatingPointError("larvanet_amd: an activation exceeded the fp16 range (|v| > 65504 or not finite) "
+                                     "under --precision fp16; run this model with --precision fp32")
+
+    def fp16_overflowed(self):
+        """True if an fp16 inference forward (fwd_runtime included) overflowed since the last check; clears the flag.
+        Always False at --precision fp32."""
+        return self._precision() == "fp16" and self.model.half_forward().take_overflow()
+
+    def _infer_checked(self, x):
+        self._clear_overflow()
+        out = self._infer(x)
+        self._check_overflow()
+        return out
+
     def _to_input_tensor(self, input_list):
         arr = np.ascontiguousarray(np.stack([np.asarray(a, dtype=np.float32) for a in input_list]))
         return torch.from_numpy(arr).to(self.device)
@@ -902,12 +964,12 @@ class LarvaNet(BaseModel):
     def upscale(self, input_list, scale):
         """list of CHW numpy images -> (N, 3, 4H, 4W) float32 numpy (models/LarvaNet.py:163-171)."""
         with torch.no_grad():
-            return self._infer(self._to_input_tensor(input_list)).detach().cpu().numpy()
+            return self._infer_checked(self._to_input_tensor(input_list)).detach().cpu().numpy()
 
     def upscale_tensor(self, input_list):
         """upscale() without the trip to the host: (N, 3, 4H, 4W) float32 on self.device."""
         with torch.no_grad():
-            return self._infer(self._to_input_tensor(input_list)).detach().clone()
+            return self._infer_checked(self._to_input_tensor(input_list)).detach().clone()
 
     def receptive_halo(self):
         """LR pixels beyond an output pixel's own LR pixel that can influence it: one per 3x3
@@ -919,7 +981,7 @@ class LarvaNet(BaseModel):
     def test(self, input_list):
         if torch.is_grad_enabled():
             return self.model(self._to_input_tensor(input_list))
-        return self._infer(self._to_input_tensor(input_list)).clone()
+        return self._infer_checked(self._to_input_tensor(input_list)).clone()
 
     def fwd_runtime(self, input_tensor):
         """models/LarvaNet.py:200-202; under torch.no_grad() a repeated shape replays a captured graph and
