@@ -326,6 +326,16 @@ int larva_gather_patches(const unsigned char* data, const long long* offsets, co
 int larva_sqerr_u8(const float* out, const unsigned char* truth, int C, int H, int W, int TH, int TW,
                    unsigned long long* acc, void* stream);
 
+/* ---- 8-bit images (uint8 in, uint8 out) --------------------------------------------------------
+ * larva_u8_hwc_to_f32_chw: in uint8 [N][H][W][3] (a decoded PNG) -> out float [N][3][H][W], exact.
+ * larva_f32_chw_to_u8_hwc: in float [N][3][H][W] -> out uint8 [N][H][W][3], q = min(max(rint(v), 0), 255): round half to
+ * even, then clamp -- larva_sqerr_u8's arithmetic, numpy's clip(round(v), 0, 255) for every finite v (and for +-inf);
+ * a NaN becomes 0.  Any N, H, W >= 1.  Where H W is a multiple of 4 and both pointers are 16-byte aligned a lane moves
+ * 4 pixels (16-byte accesses per colour plane, 12 contiguous bytes of the uint8 image), otherwise one; the values do not
+ * depend on the path. */
+int larva_u8_hwc_to_f32_chw(const unsigned char* in, float* out, int N, int H, int W, void* stream);
+int larva_f32_chw_to_u8_hwc(const float* in, unsigned char* out, int N, int H, int W, void* stream);
+
 /* ---- fp16 inference (--precision fp16; csrc/conv3x3_f16.hip) -------------------------------------
  * Grad-free x4 forward at 48 channels on v_mfma_f32_16x16x32_f16: fp16 storage, fp32 accumulation.  fp16 tensors are
  * uint16_t bit images of IEEE half, CHANNELS-LAST [N][H][W][48] (not the fp32 NCHW of the entry points above); images
@@ -355,6 +365,12 @@ int larva_f16_conv3x3(const uint16_t* const* srcs, int nsrc, const uint16_t* wpk
  * fp32 x4 base image (larva_upsample4_fwd). */
 int larva_f16_conv3x3_shuffle_base(const uint16_t* src, const uint16_t* wpk, const float* bias, const float* base,
                                    float* out, int N, int H, int W, void* stream);
+
+/* The same leg end as a uint8 image: out uint8 [N][4H][4W][3] = larva_f32_chw_to_u8_hwc of what
+ * larva_f16_conv3x3_shuffle_base stores, bit for bit, without the fp32 HR image ever reaching memory.  Sets *flag when a
+ * value it quantises is not finite. */
+int larva_f16_conv3x3_shuffle_base_u8(const uint16_t* src, const uint16_t* wpk, const float* bias, const float* base,
+                                      unsigned char* out, unsigned* flag, int N, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

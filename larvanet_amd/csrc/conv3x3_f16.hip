@@ -13,7 +13,8 @@
 //       M tile), [src][ks 14][m 3][lane 64][8 halves]; a wave loads all 42 fragments into registers once.
 //   B = pixels   [k][pixel]: lane l reads group g = 4 ks + (l >> 4) of pixel (l & 15) + tap offset from the LDS halo.
 //   C/D: lane l holds pixel (l & 15), outputs 16 m + 4 (l >> 4) + r, r = 0..3: four consecutive channels, one 8-byte
-//       fp16 store (or, for the leg end, four consecutive HR pixels of one colour: one 16-byte fp32 store).
+//       fp16 store (or, for the leg end, four consecutive HR pixels of one colour: one 16-byte fp32 store; its uint8
+//       form gathers the lane's three colours of those pixels into 12 contiguous bytes of an HWC image).
 // The input halo (6 rows x 66 columns x 48 channels) is staged in LDS with a pixel pitch of 112 bytes (7 slots of
 // 16 B, coprime to the 16 slots of a bank row), so 16 consecutive pixels of a ds_read_b128 hit 16 distinct slots.
 // A multi-source conv (the V2 merge conv over M body outputs, no concatenation) repeats weights + halo + 14 K-steps
@@ -24,7 +25,8 @@
 //
 // Overflow: an epilogue that stores fp16 sets *flag = 1 (a plain vector store; every writer stores the same value)
 // when the pre-activation value is not finite, or the stored value is not finite or exceeds 65504 in magnitude.  The
-// pre-activation test catches a NaN that the ReLU would otherwise turn into 0.
+// pre-activation test catches a NaN that the ReLU would otherwise turn into 0.  The uint8 leg end sets it when the fp32
+// value it is about to quantise is not finite (the fp32 leg end stores that value as it is).
 #include <stdint.h>
 
 #include "larva_common.h"
@@ -50,7 +52,7 @@ constexpr int kFragsPerSrc = kKSteps * kMT * 64;   // 16-byte fragments of the w
 constexpr int kMaxSrc = 8;
 constexpr float kHalfMax = 65504.f;
 
-enum Epi { EPI_BIAS = 0, EPI_RELU = 1, EPI_RES0 = 2, EPI_RES01 = 3, EPI_SHUFFLE = 4 };
+enum Epi { EPI_BIAS = 0, EPI_RELU = 1, EPI_RES0 = 2, EPI_RES01 = 3, EPI_SHUFFLE = 4, EPI_SHUFFLE_U8 = 5 };
 
 struct ConvArgs {
   const uint16_t* src[kMaxSrc];
@@ -60,10 +62,11 @@ struct ConvArgs {
   const uint16_t* res0;
   const uint16_t* res1;
   uint16_t* out;           // fp16 [N][H][W][48]            (EPI_BIAS .. EPI_RES01)
-  const float* base;       // fp32 [N][3][4H][4W]           (EPI_SHUFFLE)
+  const float* base;       // fp32 [N][3][4H][4W]           (EPI_SHUFFLE, EPI_SHUFFLE_U8)
   float* out_hr;           // fp32 [N][3][4H][4W]           (EPI_SHUFFLE)
   unsigned* flag;
   int H, W, tiles_x, tiles_y;
+  unsigned char* out_u8;   // uint8 [N][4H][4W][3]          (EPI_SHUFFLE_U8)
 };
 
 __device__ __forceinline__ h8 as_h8(uint4 v) { return __builtin_bit_cast(h8, v); }
@@ -134,6 +137,7 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
     const int x = x0 + nt * 16 + col;
     if (x >= W) continue;
     const size_t pix = ((size_t)n * H + y) * W + x;
+    f4 rgb[kMT];   // (EPI_SHUFFLE_U8: the three colours of this lane's four HR pixels)
 #pragma unroll
     for (int m = 0; m < kMT; ++m) {
       const int c0 = 16 * m + 4 * hq;
@@ -144,6 +148,13 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
         const size_t o = (((size_t)n * 3 + m) * (4 * H) + 4 * y + hq) * (size_t)(4 * W) + 4 * (size_t)x;
         const f4 bs = *reinterpret_cast<const f4*>(a.base + o);
         *reinterpret_cast<f4*>(a.out_hr + o) = v + bs;
+      } else if constexpr (EPI == EPI_SHUFFLE_U8) {
+        // the same fp32 value EPI_SHUFFLE stores; a non-finite one raises the flag instead of becoming a byte silently
+        const size_t o = (((size_t)n * 3 + m) * (4 * H) + 4 * y + hq) * (size_t)(4 * W) + 4 * (size_t)x;
+        const f4 bs = *reinterpret_cast<const f4*>(a.base + o);
+        rgb[m] = v + bs;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bad |= !__builtin_isfinite(rgb[m][r]);
       } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r) bad |= !__builtin_isfinite(v[r]);
@@ -169,6 +180,11 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
         }
         *reinterpret_cast<h4*>(a.out + pix * kC + c0) = o;
       }
+    }
+    if constexpr (EPI == EPI_SHUFFLE_U8) {
+      // R, G, B of HR row 4 y + hq, HR columns 4 x .. 4 x + 3: 12 contiguous bytes of the HWC image (192 per quarter-wave)
+      const size_t o = (((size_t)n * (4 * H) + 4 * y + hq) * (size_t)(4 * W) + 4 * (size_t)x) * 3;
+      *reinterpret_cast<rgb4_bytes*>(a.out_u8 + o) = pack_rgb4(rgb[0], rgb[1], rgb[2]);
     }
   }
   if (bad) *a.flag = 1u;
@@ -251,6 +267,7 @@ static int launch_conv(int epi, ConvArgs& a, int N, hipStream_t s) {
     case EPI_RELU: hipLaunchKernelGGL(conv_kernel<EPI_RELU>, grid, block, 0, s, a); break;
     case EPI_RES0: hipLaunchKernelGGL(conv_kernel<EPI_RES0>, grid, block, 0, s, a); break;
     case EPI_RES01: hipLaunchKernelGGL(conv_kernel<EPI_RES01>, grid, block, 0, s, a); break;
+    case EPI_SHUFFLE_U8: hipLaunchKernelGGL(conv_kernel<EPI_SHUFFLE_U8>, grid, block, 0, s, a); break;
     default: hipLaunchKernelGGL(conv_kernel<EPI_SHUFFLE>, grid, block, 0, s, a); break;
   }
   return (int)hipGetLastError();
@@ -322,6 +339,22 @@ int larva_f16_conv3x3_shuffle_base(const uint16_t* src, const uint16_t* wpk, con
   a.H = H;
   a.W = W;
   return launch_conv(EPI_SHUFFLE, a, N, (hipStream_t)stream);
+}
+
+int larva_f16_conv3x3_shuffle_base_u8(const uint16_t* src, const uint16_t* wpk, const float* bias, const float* base,
+                                      unsigned char* out, unsigned* flag, int N, int H, int W, void* stream) {
+  if (!src || !wpk || !bias || !base || !out || !flag || !shape_ok(N, H, W)) return (int)hipErrorInvalidValue;
+  ConvArgs a = {};
+  a.src[0] = src;
+  a.nsrc = 1;
+  a.wpk = wpk;
+  a.bias = bias;
+  a.base = base;
+  a.out_u8 = out;
+  a.flag = flag;
+  a.H = H;
+  a.W = W;
+  return launch_conv(EPI_SHUFFLE_U8, a, N, (hipStream_t)stream);
 }
 
 }  // extern "C"

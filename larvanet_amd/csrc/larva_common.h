@@ -124,4 +124,26 @@ __device__ __forceinline__ unsigned lds_addr_of(const float* p) {
   return __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)((__attribute__((address_space(3))) const char*)p));
 }
 
+// uint8 image output (larva_f32_chw_to_u8_hwc, the fp16 leg end's uint8 epilogue): round half to even, then clamp --
+// the arithmetic of sqerr_u8_kernel and of metrics.image_to_uint8.  A NaN becomes 0 (fmaxf returns its other operand).
+__device__ __forceinline__ unsigned quantize_u8(float v) { return (unsigned)fminf(fmaxf(rintf(v), 0.f), 255.f); }
+
+// R, G, B of four consecutive pixels -> their 12 interleaved bytes (little endian: byte 3 p + c of the run).
+struct rgb4_bytes {
+  unsigned d[3];
+};
+__device__ __forceinline__ rgb4_bytes pack_rgb4(const f32x4 r, const f32x4 g, const f32x4 b) {
+  unsigned q[12];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    q[3 * p + 0] = quantize_u8(r[p]);
+    q[3 * p + 1] = quantize_u8(g[p]);
+    q[3 * p + 2] = quantize_u8(b[p]);
+  }
+  rgb4_bytes o;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) o.d[i] = q[4 * i] | (q[4 * i + 1] << 8) | (q[4 * i + 2] << 16) | (q[4 * i + 3] << 24);
+  return o;
+}
+
 }  // namespace larva

@@ -637,6 +637,68 @@ static inline int grid_for(long long work, int block) {
   return (int)g;
 }
 
+// ---------------------------------------------------------------------------------------------
+// 8-bit images.  in uint8 [N][H][W][3] (a decoded PNG) -> out float [N][3][H][W], exact; and the way back,
+// float [N][3][H][W] -> uint8 [N][H][W][3] through quantize_u8.  Both layouts are contiguous over the H W pixels of one
+// image, so the kernels walk pixels, not rows: a row's 3 W bytes need no alignment of their own.  VEC: a lane owns 4
+// consecutive pixels -- 12 bytes of the uint8 image (three 4-byte accesses) and one 16-byte access per colour plane;
+// valid when H W is a multiple of 4 (every image and plane then starts on such a boundary) and both base pointers are
+// 16-byte aligned.  Otherwise one pixel per lane with scalar accesses; the values are the same either way.
+// ---------------------------------------------------------------------------------------------
+template <bool VEC>
+__global__ __launch_bounds__(256) void u8_hwc_to_f32_chw_kernel(const unsigned char* __restrict__ in,
+                                                                float* __restrict__ out, long long HW,
+                                                                long long total) {
+  // total: pixel quads (VEC) or pixels of the whole batch
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    if constexpr (VEC) {
+      const long long per = HW >> 2, n = i / per, q = i - n * per;
+      const unsigned* src = reinterpret_cast<const unsigned*>(in) + 3 * i;
+      const unsigned d0 = src[0], d1 = src[1], d2 = src[2];
+      const unsigned b[12] = {d0 & 255u, (d0 >> 8) & 255u, (d0 >> 16) & 255u, d0 >> 24,
+                              d1 & 255u, (d1 >> 8) & 255u, (d1 >> 16) & 255u, d1 >> 24,
+                              d2 & 255u, (d2 >> 8) & 255u, (d2 >> 16) & 255u, d2 >> 24};
+      float* dst = out + n * 3 * HW + 4 * q;
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        *reinterpret_cast<f32x4*>(dst + c * HW) = f32x4{(float)b[c], (float)b[3 + c], (float)b[6 + c], (float)b[9 + c]};
+    } else {
+      const long long n = i / HW, p = i - n * HW;
+      const unsigned char* src = in + 3 * i;
+      float* dst = out + n * 3 * HW + p;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) dst[c * HW] = (float)src[c];
+    }
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void f32_chw_to_u8_hwc_kernel(const float* __restrict__ in,
+                                                                unsigned char* __restrict__ out, long long HW,
+                                                                long long total) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    if constexpr (VEC) {
+      const long long per = HW >> 2, n = i / per, q = i - n * per;
+      const float* src = in + n * 3 * HW + 4 * q;
+      const f32x4 r = *reinterpret_cast<const f32x4*>(src);
+      const f32x4 g = *reinterpret_cast<const f32x4*>(src + HW);
+      const f32x4 b = *reinterpret_cast<const f32x4*>(src + 2 * HW);
+      *reinterpret_cast<rgb4_bytes*>(out + 12 * i) = pack_rgb4(r, g, b);
+    } else {
+      const long long n = i / HW, p = i - n * HW;
+      const float* src = in + n * 3 * HW + p;
+      unsigned char* dst = out + 3 * i;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) dst[c] = (unsigned char)quantize_u8(src[c * HW]);
+    }
+  }
+}
+
+static inline bool u8_vec_ok(const void* a, const void* b, long long HW) {
+  return HW % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0;
+}
 
 }  // namespace larva
 
@@ -916,6 +978,42 @@ int larva_sqerr_u8(const float* out, const unsigned char* truth, int C, int H, i
   if (!out || !truth || !acc || C <= 0 || H <= 0 || W <= 0 || TH < H || TW < W) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(sqerr_u8_kernel, dim3(grid_for((long long)C * H * W, 256)), dim3(256), 0, (hipStream_t)stream,
                      out, truth, C, H, W, TH, TW, acc);
+  return (int)hipGetLastError();
+}
+
+static bool image_shape_ok(int N, int H, int W) {
+  return N > 0 && H > 0 && W > 0 && (long long)N * H * W * 3 < (1ll << 40);
+}
+
+// out float [N][3][H][W] = in uint8 [N][H][W][3], exact.
+int larva_u8_hwc_to_f32_chw(const unsigned char* in, float* out, int N, int H, int W, void* stream) {
+  if (!in || !out || !image_shape_ok(N, H, W)) return (int)hipErrorInvalidValue;
+  const long long HW = (long long)H * W;
+  if (u8_vec_ok(in, out, HW)) {
+    const long long total = N * (HW / 4);
+    hipLaunchKernelGGL(u8_hwc_to_f32_chw_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, in,
+                       out, HW, total);
+  } else {
+    const long long total = N * HW;
+    hipLaunchKernelGGL(u8_hwc_to_f32_chw_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, in,
+                       out, HW, total);
+  }
+  return (int)hipGetLastError();
+}
+
+// out uint8 [N][H][W][3] = clip(rint(in), 0, 255) of in float [N][3][H][W].
+int larva_f32_chw_to_u8_hwc(const float* in, unsigned char* out, int N, int H, int W, void* stream) {
+  if (!in || !out || !image_shape_ok(N, H, W)) return (int)hipErrorInvalidValue;
+  const long long HW = (long long)H * W;
+  if (u8_vec_ok(in, out, HW)) {
+    const long long total = N * (HW / 4);
+    hipLaunchKernelGGL(f32_chw_to_u8_hwc_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, in,
+                       out, HW, total);
+  } else {
+    const long long total = N * HW;
+    hipLaunchKernelGGL(f32_chw_to_u8_hwc_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, in,
+                       out, HW, total);
+  }
   return (int)hipGetLastError();
 }
 

@@ -3,7 +3,8 @@ csrc/conv3x3_f16.hip, over the parameters of the existing module tree (head, bod
 
 Activations are fp16 channels-last [N][H][W][48]; every conv accumulates in fp32 and rounds its epilogue's result
 (bias, ReLU, residual adds) once to fp16.  The image going in and the HR image coming out are fp32 NCHW, and the base
-image is the fp32 path's own bicubic / bilinear kernel, so only the internal activations change precision.  Training,
+image is the fp32 path's own bicubic / bilinear kernel, so only the internal activations change precision.  The uint8
+image path (upscale_u8) ends in the leg end's uint8 epilogue instead: the same fp32 values, stored as HWC bytes.  Training,
 validate_for_train and every grad-enabled call stay on the fp32 path (the plugins only dispatch here without
 gradients).
 
@@ -108,18 +109,22 @@ class HalfForward:
             fea = self._conv(blk.body[2], h, flag, res0=fea, res1=x if j == len(blocks) - 1 else None)
         return fea
 
-    def _leg_end(self, recon_block, fea, base, flag):
+    def _leg_end(self, recon_block, fea, base, flag, u8=False):
         c1, c2 = recon_block[0], recon_block[2]
         h = self._conv(c1, fea, flag, relu=True)
+        if u8:   # the same fp32 values, rounded and clamped to bytes in the conv's epilogue
+            return K.f16_conv3x3_shuffle_base_u8(h, self._wpk(c2), c2.bias.detach(), base, flag)
         return K.f16_conv3x3_shuffle_base(h, self._wpk(c2), c2.bias.detach(), base)
 
-    def __call__(self, x):
+    def __call__(self, x, u8=False):
+        """fp32 [N][3][H][W] -> the fp32 [N][3][4H][4W] image, or with u8 its uint8 [N][4H][4W][3] form
+        (K.f32_chw_to_u8_hwc of the former, bit for bit)."""
         net = self.net
         x = x.contiguous()
         base = net.base(x)
         legs = getattr(net, "leg", None)
         if legs == 0:
-            return base
+            return K.f32_chw_to_u8_hwc(base) if u8 else base
         flag = self.flag(x.device)
         head = net.head.feature_extraction
         fea = K.f16_head(x, head.weight.detach(), head.bias.detach(), flag)
@@ -130,5 +135,5 @@ class HalfForward:
             feats.append(fea)
         if legs is None and hasattr(net, "tail"):
             fea = self._conv(net.tail.merge_conv, feats, flag)
-            return self._leg_end(net.tail.recon_block, fea, base, flag)
-        return self._leg_end(getattr(net, "body_%d" % (nb - 1)).leg.recon_block, fea, base, flag)
+            return self._leg_end(net.tail.recon_block, fea, base, flag, u8)
+        return self._leg_end(getattr(net, "body_%d" % (nb - 1)).leg.recon_block, fea, base, flag, u8)

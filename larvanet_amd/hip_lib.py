@@ -138,6 +138,13 @@ SIGNATURES = {
                                          ctypes.c_int, ctypes.c_void_p]),
     "larva_f16_conv3x3_shuffle_base": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p, _c_float_p,
                                                       ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "larva_f16_conv3x3_shuffle_base_u8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p,
+                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                         ctypes.c_int, ctypes.c_void_p]),
+    "larva_u8_hwc_to_f32_chw": (ctypes.c_int, [ctypes.c_void_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_void_p]),
+    "larva_f32_chw_to_u8_hwc": (ctypes.c_int, [_c_float_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_void_p]),
 }
 
 _lib = None

@@ -971,3 +971,63 @@ def f16_conv3x3_shuffle_base(src, wpk, bias, base):
     hip_lib.check(lib.larva_f16_conv3x3_shuffle_base(src.data_ptr(), wpk.data_ptr(), bias.data_ptr(), base.data_ptr(),
                                                      out.data_ptr(), N, H, W, _stream()), "larva_f16_conv3x3_shuffle_base")
     return out
+
+
+def f16_conv3x3_shuffle_base_u8(src, wpk, bias, base, flag, out=None):
+    """The leg end as a uint8 image: uint8 [N][4H][4W][3] = f32_chw_to_u8_hwc(f16_conv3x3_shuffle_base(...)), bit for
+    bit, in one launch (the fp32 HR image is never stored).  A non-finite value sets `flag`."""
+    lib = hip_lib.load()
+    _chk16(src, "src")
+    N, H, W = (int(v) for v in src.shape[:3])
+    if wpk.dtype != torch.float16 or not wpk.is_cuda or wpk.numel() != f16_packed_weight_halves(F16_CHANNELS, F16_CHANNELS):
+        raise RuntimeError("larvanet_amd: wpk is not the fp16 image of a 48 -> 48 conv")
+    _chk(bias, "bias", (F16_CHANNELS,))
+    _chk(base, "base", (N, 3, 4 * H, 4 * W))
+    if out is None:
+        out = torch.empty((N, 4 * H, 4 * W, 3), device=src.device, dtype=torch.uint8)
+    _chk_u8(out, "out", (N, 4 * H, 4 * W, 3))
+    hip_lib.check(lib.larva_f16_conv3x3_shuffle_base_u8(src.data_ptr(), wpk.data_ptr(), bias.data_ptr(), base.data_ptr(),
+                                                        out.data_ptr(), _chk_flag(flag), N, H, W, _stream()),
+                  "larva_f16_conv3x3_shuffle_base_u8")
+    return out
+
+
+# ------------------------------------------------------------------ 8-bit images (csrc/larva_pointwise.hip)
+def _chk_u8(t, name, shape=None):
+    """A uint8 image batch [N][H][W][3] (torch.uint8, contiguous, on the device)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("larvanet_amd: %s must be a tensor on a HIP device (no CPU path exists)" % name)
+    if t.dtype != torch.uint8 or not t.is_contiguous():
+        raise RuntimeError("larvanet_amd: %s must be a contiguous uint8 tensor, got %s" % (name, t.dtype))
+    if t.dim() != 4 or int(t.shape[3]) != 3:
+        raise RuntimeError("larvanet_amd: %s must be [N][H][W][3], got %s" % (name, tuple(t.shape)))
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise RuntimeError("larvanet_amd: %s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
+    return t.data_ptr()
+
+
+def u8_hwc_to_f32_chw(x, out=None):
+    """uint8 [N][H][W][3] (decoded images) -> float32 [N][3][H][W], exact."""
+    lib = hip_lib.load()
+    _chk_u8(x, "x")
+    N, H, W = (int(v) for v in x.shape[:3])
+    if out is None:
+        out = torch.empty((N, 3, H, W), device=x.device, dtype=torch.float32)
+    _chk(out, "out", (N, 3, H, W))
+    hip_lib.check(lib.larva_u8_hwc_to_f32_chw(x.data_ptr(), out.data_ptr(), N, H, W, _stream()), "larva_u8_hwc_to_f32_chw")
+    return out
+
+
+def f32_chw_to_u8_hwc(x, out=None):
+    """float32 [N][3][H][W] -> uint8 [N][H][W][3] = clip(round half to even(x), 0, 255): metrics.image_to_uint8 on the
+    device, transposed for an image writer."""
+    lib = hip_lib.load()
+    _chk(x, "x")
+    if x.dim() != 4 or int(x.shape[1]) != 3:
+        raise RuntimeError("larvanet_amd: x must be [N][3][H][W], got %s" % (tuple(x.shape),))
+    N, _, H, W = (int(v) for v in x.shape)
+    if out is None:
+        out = torch.empty((N, H, W, 3), device=x.device, dtype=torch.uint8)
+    _chk_u8(out, "out", (N, H, W, 3))
+    hip_lib.check(lib.larva_f32_chw_to_u8_hwc(x.data_ptr(), out.data_ptr(), N, H, W, _stream()), "larva_f32_chw_to_u8_hwc")
+    return out

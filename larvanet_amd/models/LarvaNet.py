@@ -904,7 +904,8 @@ class LarvaNet(BaseModel):
         graph.replay()
         return out
 
-    def _capture_infer(self, x):
+    def _capture_infer(self, x, forward=None):
+        forward = forward or self._forward_nograd
         static_x = x.clone()
         try:
             side = torch.cuda.Stream()
@@ -912,12 +913,12 @@ class LarvaNet(BaseModel):
             with torch.cuda.stream(side):
                 for _ in range(2):
                     with self._infer_scope():
-                        self._forward_nograd(static_x)
+                        forward(static_x)
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
                 with self._infer_scope():
-                    out = self._forward_nograd(static_x)
+                    out = forward(static_x)
             return static_x, graph, out
         except Exception as e:   # an optimisation only
             if self.strict_graph:
@@ -970,6 +971,93 @@ class LarvaNet(BaseModel):
         """upscale() without the trip to the host: (N, 3, 4H, 4W) float32 on self.device."""
         with torch.no_grad():
             return self._infer_checked(self._to_input_tensor(input_list)).detach().clone()
+
+    # ------------------------------------------------------------------ 8-bit images in, 8-bit images out
+    def _forward_nograd_u8(self, x_u8):
+        """uint8 [N][H][W][3] -> uint8 [N][sH][sW][3] (no graph): the float forward over the exactly converted image,
+        then round half to even + clamp on the device.  At fp16 the leg end's epilogue stores the bytes itself."""
+        x = K.u8_hwc_to_f32_chw(x_u8)
+        if self._precision() == "fp16":
+            return self.model.half_forward()(x, u8=True)
+        return K.f32_chw_to_u8_hwc(self.model(x).contiguous())
+
+    def _infer_u8(self, x_u8):
+        """_infer for the uint8 path, with the same rules (second sight of a shape captures, large images run
+        eagerly).  Its graphs are kept under (shape, precision, "u8") in a table of their own (_infer_graphs_u8, with
+        its own limit of four), so the float path captures exactly what it did without this one.  A replay returns the
+        graph's output buffer."""
+        if not self.use_hip_graph or is_large_inference(x_u8.shape[0], x_u8.shape[1], x_u8.shape[2]):
+            return self._forward_nograd_u8(x_u8)
+        cache = self.__dict__.setdefault("_infer_graphs_u8", {})
+        seen = self.__dict__.setdefault("_infer_seen_u8", {})
+        key = (tuple(x_u8.shape), self._precision(), "u8")
+        ent = cache.get(key)
+        if ent is None:
+            if len(seen) > 512:
+                seen.clear()
+            seen[key] = seen.get(key, 0) + 1
+            if seen[key] < 2 or len(cache) >= 4:
+                return self._forward_nograd_u8(x_u8)
+            ent = cache[key] = self._capture_infer(x_u8, self._forward_nograd_u8)
+        if ent is False:
+            return self._forward_nograd_u8(x_u8)
+        if self._precision() == "fp16":
+            self.model.half_forward().refresh()
+        else:
+            for pc in self.model.packed_convs():
+                pc.refresh()
+        static_x, graph, out = ent
+        static_x.copy_(x_u8)
+        graph.replay()
+        return out
+
+    def _check_u8_images(self, input_list, scale):
+        """Host-side argument checks of upscale_u8 (before any device work) -> the (N, H, W, 3) uint8 batch."""
+        if int(scale) != self.scale:
+            raise ValueError("larvanet_amd: this model upscales by %d, not by %r" % (self.scale, scale))
+        if isinstance(input_list, np.ndarray) or not len(input_list):
+            raise ValueError("larvanet_amd: upscale_u8 takes a non-empty list of (H, W, 3) uint8 arrays")
+        for a in input_list:
+            if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
+                raise TypeError("larvanet_amd: upscale_u8 takes uint8 numpy arrays (decoded images), got %s"
+                                % (getattr(a, "dtype", type(a).__name__),))
+            if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+                raise ValueError("larvanet_amd: upscale_u8 takes (H, W, 3) images, got shape %s" % (a.shape,))
+            if a.shape != input_list[0].shape:
+                raise ValueError("larvanet_amd: the images of one upscale_u8 call must have one shape, got %s and %s"
+                                 % (input_list[0].shape, a.shape))
+        return np.ascontiguousarray(np.stack(input_list))
+
+    def _check_u8_tensor(self, x_u8):
+        if not isinstance(x_u8, torch.Tensor) or x_u8.dtype != torch.uint8:
+            raise TypeError("larvanet_amd: upscale_u8_tensor takes a uint8 tensor, got %s"
+                            % (getattr(x_u8, "dtype", type(x_u8).__name__),))
+        if x_u8.dim() != 4 or x_u8.shape[3] != 3 or min(x_u8.shape) < 1:
+            raise ValueError("larvanet_amd: upscale_u8_tensor takes [N][H][W][3], got shape %s" % (tuple(x_u8.shape),))
+        _require_hip(x_u8)
+        return x_u8.contiguous()
+
+    def _infer_u8_checked(self, x_u8):
+        self._clear_overflow()
+        out = self._infer_u8(x_u8)
+        self._check_overflow()
+        return out
+
+    def upscale_u8(self, input_list, scale):
+        """list of uint8 (H, W, 3) images of one shape -> uint8 (N, sH, sW, 3) numpy:
+        image_to_uint8(upscale(...)) byte for byte, transposed for an image writer, with a quarter of the bytes crossing
+        the host link and no pass over the image on the host."""
+        batch = self._check_u8_images(input_list, scale)
+        with torch.no_grad():
+            x = torch.from_numpy(batch).to(self.device)
+            _require_hip(x)
+            return self._infer_u8_checked(x).cpu().numpy()
+
+    def upscale_u8_tensor(self, x_u8):
+        """upscale_u8 without the trips to and from the host: uint8 [N][H][W][3] on self.device -> uint8 [N][sH][sW][3]."""
+        x = self._check_u8_tensor(x_u8)
+        with torch.no_grad():
+            return self._infer_u8_checked(x).clone()
 
     def receptive_halo(self):
         """LR pixels beyond an output pixel's own LR pixel that can influence it: one per 3x3

@@ -1,0 +1,148 @@
+"""Images in, images out, with the host link hidden behind the forward.
+
+upscale_stream() walks an iterable of uint8 (H, W, 3) images of any mix of sizes through model._infer_u8 and yields the
+uint8 (sH, sW, 3) results in input order.  Image i+1's host-to-device copy and image i-1's device-to-host copy run on
+ONE extra stream beside image i's forward:
+
+    copy stream     H2D(0) H2D(1) D2H(0) H2D(2) D2H(1) ...        (issue order; D2H(i) waits for forward i's event)
+    compute stream         fwd(0)        fwd(1)        fwd(2) ...  (fwd(i) waits for H2D(i)'s event)
+
+Every buffer a copy touches belongs to the pipeline: `depth` slots of flat pinned and device buffers, grown to the
+largest image seen and viewed at each image's size.  The forward's result is copied (device to device, ~10 us for an
+8 MB image) into the slot's own output buffer on the compute stream, because a replayed graph's output buffer is
+overwritten by the next image of that shape and an eager result is the caching allocator's, which knows nothing of
+the copy stream.  A slot is reused only after its device-to-host copy has been waited for, which orders every reuse.
+"""
+import collections
+
+import numpy as np
+import torch
+
+
+class _Slot:
+    """The staging buffers of one image in flight."""
+
+    def __init__(self, device, copy_stream):
+        self.device = device
+        self.copy_stream = copy_stream
+        self.pin_in = self.pin_out = self.dev_in = self.dev_out = None
+        self.pin_flag = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+        self.dev_flag = torch.zeros(1, dtype=torch.int32, device=device)
+        self.dev_flag.record_stream(copy_stream)
+        self.h2d = torch.cuda.Event()
+        self.fwd = torch.cuda.Event()
+        self.done = torch.cuda.Event()
+        self.out_shape = None
+        self.d2h_issued = False
+
+    def _grown(self, buf, n, pinned):
+        if buf is not None and buf.numel() >= n:
+            return buf
+        n = -(-n // (1 << 20)) << 20   # whole MiB: a slightly larger image does not allocate again
+        if pinned:
+            return torch.empty(n, dtype=torch.uint8, pin_memory=True)
+        buf = torch.empty(n, dtype=torch.uint8, device=self.device)
+        buf.record_stream(self.copy_stream)
+        return buf
+
+    def views_in(self, shape):
+        n = int(np.prod(shape))
+        self.pin_in = self._grown(self.pin_in, n, True)
+        self.dev_in = self._grown(self.dev_in, n, False)
+        return self.pin_in[:n].view(shape), self.dev_in[:n].view(shape)
+
+    def views_out(self, shape):
+        n = int(np.prod(shape))
+        self.pin_out = self._grown(self.pin_out, n, True)
+        self.dev_out = self._grown(self.dev_out, n, False)
+        return self.pin_out[:n].view(shape), self.dev_out[:n].view(shape)
+
+
+def _check_image(a):
+    if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
+        raise TypeError("larvanet_amd: upscale_stream takes uint8 numpy arrays (decoded images), got %s"
+                        % (getattr(a, "dtype", type(a).__name__),))
+    if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("larvanet_amd: upscale_stream takes (H, W, 3) images, got shape %s" % (a.shape,))
+
+
+def upscale_stream(model, images, scale, depth=2):
+    """Generator: uint8 (H, W, 3) numpy images of any sizes -> their uint8 (sH, sW, 3) upscaled images, in input order;
+    each result equals model.upscale_u8([image], scale)[0].  At most `depth` images are in flight (depth 1 = no overlap).
+    Under --precision fp16 an image whose activations overflow raises FloatingPointError when its turn to be yielded
+    comes; the images before it have been yielded.  The yielded arrays are the caller's (copies of the pinned staging
+    buffers)."""
+    depth = int(depth)
+    if depth < 1:
+        raise ValueError("larvanet_amd: upscale_stream needs depth >= 1")
+    if int(scale) != model.scale:
+        raise ValueError("larvanet_amd: this model upscales by %d, not by %r" % (model.scale, scale))
+    if model.device.type != "cuda":
+        raise RuntimeError("larvanet_amd: upscale_stream only runs on a HIP device (MI355X); there is no CPU fallback")
+    return _stream(model, images, depth)
+
+
+def _stream(model, images, depth):
+    fp16 = model._precision() == "fp16"
+    compute = torch.cuda.current_stream()
+    copy = torch.cuda.Stream()
+    free = [_Slot(model.device, copy) for _ in range(depth)]
+    inflight = collections.deque()
+    model_flag = model.model.half_forward().flag(model.device) if fp16 else None
+
+    def issue_d2h(slot):
+        if slot.d2h_issued:
+            return
+        pin_out, dev_out = slot.views_out(slot.out_shape)
+        with torch.cuda.stream(copy):
+            copy.wait_event(slot.fwd)
+            pin_out.copy_(dev_out, non_blocking=True)
+            if fp16:
+                slot.pin_flag.copy_(slot.dev_flag, non_blocking=True)
+            slot.done.record(copy)
+        slot.d2h_issued = True
+
+    def retire(slot):
+        issue_d2h(slot)
+        slot.done.synchronize()
+        if fp16 and int(slot.pin_flag[0]):
+            raise FloatingPointError("larvanet_amd: an activation exceeded the fp16 range (|v| > 65504 or not finite) "
+                                     "under --precision fp16; run this model with --precision fp32")
+        out = np.array(slot.views_out(slot.out_shape)[0].numpy()[0])
+        free.append(slot)
+        return out
+
+    try:
+        with torch.no_grad():
+            if fp16:
+                model_flag.zero_()
+            for image in images:
+                _check_image(image)
+                if len(inflight) == depth:
+                    yield retire(inflight.popleft())
+                slot = free.pop()
+                shape = (1,) + tuple(image.shape)
+                pin_in, dev_in = slot.views_in(shape)
+                np.copyto(pin_in.numpy()[0], image)
+                with torch.cuda.stream(copy):
+                    dev_in.copy_(pin_in, non_blocking=True)
+                    slot.h2d.record(copy)
+                if inflight:   # the previous image's way back, queued behind this image's way in
+                    issue_d2h(inflight[-1])
+                compute.wait_event(slot.h2d)
+                out = model._infer_u8(dev_in)
+                slot.out_shape = tuple(out.shape)
+                slot.views_out(slot.out_shape)[1].copy_(out)
+                if fp16:   # this image's overflow verdict; the model's flag starts the next image clean
+                    slot.dev_flag.copy_(model_flag)
+                    model_flag.zero_()
+                slot.fwd.record(compute)
+                slot.d2h_issued = False
+                inflight.append(slot)
+            while inflight:
+                yield retire(inflight.popleft())
+    finally:
+        # (an early exit or an error: the staging buffers are released only once no copy can still touch them)
+        if inflight:
+            copy.synchronize()
+            compute.synchronize()

@@ -1,0 +1,133 @@
+"""Folder upscaler: counterpart of the reference's get_sr.py.  Every *.png of --input_path goes through the network and
+is written as <output_path>/<stem>.png.
+
+    python -m larvanet_amd.upscale_images --model=LarvaNet --num_modules=4 --num_blocks=4,4,4,4 \\
+        --restore_path=model.pth --input_path=LR --output_path=SR [--precision fp16] [--io_threads 8]
+
+The images stay 8-bit end to end (pipeline.upscale_stream over model._infer_u8): PNGs are decoded and encoded by a
+thread pool around the stream, a quarter of the float path's bytes cross the host link, and the copies of neighbouring
+images run beside the forward.  Under torchrun file i goes to rank i mod world, as validate.py shards.  The
+reference's --chop_forward is not carried over (approximate by design; image_utils has exact bands)."""
+import argparse
+import collections
+import concurrent.futures
+import importlib
+import os
+import time
+
+import numpy as np
+
+from . import dist as ldist
+
+
+def build_parser():
+    p = argparse.ArgumentParser()
+    p.add_argument("--model", type=str, default="LarvaNet")
+    p.add_argument("--scale", type=int, default=4)
+    p.add_argument("--cuda_device", type=str, default=None)
+    p.add_argument("--restore_path", type=str, default=None,
+                   help="checkpoint (bare state_dict); omitted = freshly initialised weights")
+    p.add_argument("--restore_target", type=str)
+    p.add_argument("--restore_global_step", type=int, default=0)
+    p.add_argument("--input_path", type=str, default="LR")
+    p.add_argument("--output_path", type=str, default="SR")
+    p.add_argument("--io_threads", type=int, default=None,
+                   help="PNG decode / encode threads; default and upper limit: this rank's share of the host's cores")
+    p.add_argument("--depth", type=int, default=2, help="images in flight on the device (1 = no copy overlap)")
+    return p
+
+
+def list_pngs(input_path):
+    """File names of input_path ending in .png (any letter case), sorted."""
+    return sorted(f for f in os.listdir(input_path) if f.lower().endswith(".png"))
+
+
+def shard(files, rank, world):
+    return list(files[rank::world])
+
+
+def output_name(image_name):
+    return os.path.splitext(image_name)[0] + ".png"
+
+
+def io_threads(requested):
+    """--io_threads clamped to [1, this rank's cores]; OMP_NUM_THREADS, where set, lowers the limit further."""
+    cap = ldist.host_threads()
+    try:
+        cap = max(1, min(cap, int(os.environ.get("OMP_NUM_THREADS", "") or cap)))
+    except ValueError:
+        pass
+    return cap if requested is None else max(1, min(int(requested), cap))
+
+
+def read_rgb(path):
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.ascontiguousarray(np.asarray(im.convert("RGB"), dtype=np.uint8))
+
+
+def write_rgb(image_hwc_uint8, path):
+    from PIL import Image
+    Image.fromarray(image_hwc_uint8).save(path)
+
+
+def _prefetched(pool, fn, items, ahead):
+    """fn(item) for every item in order, at most `ahead` of them running or waiting in the pool."""
+    pending = collections.deque()
+    for item in items:
+        pending.append(pool.submit(fn, item))
+        if len(pending) >= ahead:
+            yield pending.popleft().result()
+    while pending:
+        yield pending.popleft().result()
+
+
+def main(argv=None):
+    args, remaining = build_parser().parse_known_args(argv)
+    if args.cuda_device is not None and "LOCAL_RANK" not in os.environ:
+        os.environ["HIP_VISIBLE_DEVICES"] = args.cuda_device
+    rank, world = ldist.init_from_env()
+    ldist.limit_host_threads()
+    names = list_pngs(args.input_path)
+    print("data: %d images are prepared" % len(names))
+    mine = shard(names, rank, world)
+    os.makedirs(args.output_path, exist_ok=True)
+    if not mine:
+        print("finished")
+        return {}
+
+    from . import pipeline
+    print("prepare model - %s" % args.model)
+    model = importlib.import_module("larvanet_amd.models." + args.model).create_model()
+    _, remaining = model.parse_args(remaining)
+    model.prepare(is_training=False, scales=[args.scale], global_step=args.restore_global_step)
+    if remaining:
+        print("WARNING: found unhandled arguments: %s" % remaining)
+    if args.restore_path is not None:
+        model.restore(ckpt_path=args.restore_path, target=args.restore_target)
+        print("restored the model")
+
+    print("begin super-resolution")
+    threads = io_threads(args.io_threads)
+    durations = {}
+    writes = collections.deque()
+    with concurrent.futures.ThreadPoolExecutor(max_workers=threads) as pool:
+        decoded = _prefetched(pool, read_rgb, [os.path.join(args.input_path, n) for n in mine], ahead=threads + args.depth)
+        last = time.perf_counter()
+        for i, out in enumerate(pipeline.upscale_stream(model, decoded, args.scale, depth=args.depth)):
+            now = time.perf_counter()
+            durations[mine[i]] = now - last   # (time between results: the stream's rate, not one image's latency)
+            writes.append(pool.submit(write_rgb, out, os.path.join(args.output_path, output_name(mine[i]))))
+            while len(writes) > threads:   # (bounds the results waiting to be encoded)
+                writes.popleft().result()
+            print("%d/%d, %s, duration: %.4fs" % (i + 1, len(mine), mine[i], durations[mine[i]]))
+            last = time.perf_counter()
+        for w in writes:
+            w.result()
+    print("finished")
+    print("- average duration: %.4fs" % np.mean(list(durations.values())))
+    return durations
+
+
+if __name__ == "__main__":
+    main()
