@@ -777,40 +777,49 @@ class BodyFn(torch.autograd.Function):
         return (dx, None) + tuple(flat)
 
 
-class LegFn(torch.autograd.Function):
-    """LarvaLeg.forward (models/LarvaNet.py:251-267): conv+ReLU, conv -> PixelShuffle(4) -> += base,
-    the shuffle and the base add fused into the second conv's store."""
+# The x2 / x3 ends of the network (a model prepared with scales=[2] or [3]).  At scale s the last conv of a leg (and of
+# the V2 tail) has 3 s^2 = 12 / 27 outputs.  It runs as a plain-epilogue 32-output conv on zero-padded weight rows
+# (PackedConv.cout_pad), and the kernels of csrc/larva_scale.hip map its [N][32][H][W] output to the [N][3][sH][sW]
+# image and back:
+#     forward    y = conv(h) ; out = PixelShuffle(s)(y) + base                       (pixel_shuffle_base)
+#     exit       partial sums of |out - truth| and the unshuffled sign gradient, one pass (shuffle_l1_partial_grad)
+#     backward   dh = dgrad(dyl) * [h > 0] on the 32 padded gradient channels (4 K chunks, zero weight rows),
+#                dW = the (32, 48) weight-gradient kernel, only the real 12 / 27 rows reach the parameters.
+# At x4 the conv kernel's shuffle epilogue stores the image itself and the tuned x4 pointwise kernels make dyl.  LegFn
+# and ExitFn look at the scale in three places only: how the image is made from the last conv, how dyl is made, and
+# the last conv's weight gradient (_leg_backward).
+def _leg_forward(fea, base, pcs, params, scale, lw=None):
+    """The two convs of a leg -> (h, y): h = ReLU(conv1(fea)); y is the finished image PixelShuffle(4)(conv2(h)) + base
+    at x4 (the conv's shuffle epilogue), the plain padded conv output [N][cout_pad][H][P] at x2 / x3."""
+    w1, b1, w2, b2 = params
+    (f1, _), = pcs[0].get()
+    (f2, _), = pcs[1].get()
+    h = K.conv3x3(fea, f1, int(w1.shape[0]), bias=b1.detach(), relu=True, logical_w=lw)
+    if scale == 4:
+        return h, K.conv3x3(h, f2, int(w2.shape[0]), bias=b2.detach(), shuffle=True, base=base, logical_w=lw)
+    return h, K.conv3x3(h, f2, pcs[1].cout_pad, bias=pcs[1].padded_bias(), logical_w=lw)
 
-    @staticmethod
-    def forward(ctx, fea, base, pcs, w1, b1, w2, b2):
-        (f1, _), = pcs[0].get()
-        (f2, _), = pcs[1].get()
-        c = int(w1.shape[0])
-        h = K.conv3x3(fea, f1, c, bias=b1.detach(), relu=True, logical_w=_lw())
-        out = K.conv3x3(h, f2, int(w2.shape[0]), bias=b2.detach(), shuffle=True, base=base, logical_w=_lw())
-        ctx.save_for_backward(fea, h)
-        ctx.pcs = pcs
-        ctx.wshape, ctx.wshape2 = tuple(w1.shape), tuple(w2.shape)
-        return out
 
-    @staticmethod
-    def backward(ctx, dout):
-        fea, h = ctx.saved_tensors[:2]
-        pcs = ctx.pcs
-        c, c2 = ctx.wshape[0], ctx.wshape2[0]
-        (_, bw1), = pcs[0].get()
-        (_, bw2), = pcs[1].get()
-        dyl = K.pixel_unshuffle4(dout.contiguous())
-        dh = K.conv3x3(dyl, bw2, c, mask=h)
-        dfea = K.conv3x3(dh, bw1, c)
-        ((dw1, db1),), ((dw2, db2),) = _leg_wgrad([(dh, fea, ctx.wshape, 0, c) + _targets(pcs[0])],
-                                                    [(dyl, h, ctx.wshape2, 0, c) + _targets(pcs[1])], c, c2)
-        if _targets(pcs[0])[0] is not None:
-            dw1 = db1 = None
+def _leg_backward(ctx, fea, h, dyl):
+    """Backward of a leg from dyl, the gradient of its last conv's output in the pixel-unshuffled layout ->
+    (dfea, dw1, db1, dw2, db2), None where the gradient bucket owns the gradient."""
+    pcs = ctx.pcs
+    c = ctx.wshape[0]
+    (_, bw1), = pcs[0].get()
+    (_, bw2), = pcs[1].get()
+    dh = K.conv3x3(dyl, bw2, c, mask=h)
+    dfea = K.conv3x3(dh, bw1, c)
+    first = [(dh, fea, ctx.wshape, 0, c) + _targets(pcs[0])]
+    if ctx.scale == 4:
+        ((dw1, db1),), ((dw2, db2),) = _leg_wgrad(first, [(dyl, h, ctx.wshape2, 0, c) + _targets(pcs[1])], c, ctx.wshape2[0])
         if _targets(pcs[1])[0] is not None:
             dw2 = db2 = None
-        # base comes from a parameter-free interpolation of the network input: no gradient
-        return dfea, None, None, dw1, db1, dw2, db2
+    else:
+        ((dw1, db1),) = _wgrad(first, c, c, inplace=_targets(pcs[0])[0] is not None)
+        dw2, db2 = padded_wgrad(dyl, h, pcs[1], ctx.wshape2)
+    if _targets(pcs[0])[0] is not None:
+        dw1 = db1 = None
+    return dfea, dw1, db1, dw2, db2
 
 
 def _leg_wgrad(first, second, c, c2):
@@ -824,39 +833,76 @@ def _leg_wgrad(first, second, c, c2):
     return _wgrad(list(first), c, c, inplace=inplace), _wgrad(list(second), c2, c, inplace=inplace)
 
 
+def padded_wgrad(dyl, h, pc, wshape):
+    """Weight gradient of a padded-output conv from its padded output gradient dyl [N][cout_pad][H][W]: the
+    (cout_pad, cin) kernel writes a padded image, and only its real rows and biases reach the gradients (copied into the
+    bucket views when they exist) -> (dw, db), or (None, None) when written in place."""
+    cp, cin, rows = pc.cout_pad, int(wshape[1]), int(wshape[0])
+    dw = torch.empty((cp,) + tuple(wshape[1:]), device=dyl.device, dtype=torch.float32)
+    db = torch.empty((cp,), device=dyl.device, dtype=torch.float32)
+    K.conv3x3_wgrad([{"dy": dyl, "x": h, "dw": dw, "db": db, "cin_off": 0, "cin_valid": cin}], cp, cin,
+                    _splits(1, cp, cin))
+    tw, tb = _targets(pc)
+    if tw is None:
+        return dw[:rows], db[:rows]
+    tw.copy_(dw[:rows])
+    tb.copy_(db[:rows])
+    return None, None
+
+
+class LegFn(torch.autograd.Function):
+    """LarvaLeg.forward (models/LarvaNet.py:251-267): conv+ReLU, conv -> PixelShuffle(scale) -> += base; at x4 the
+    shuffle and the base add are fused into the second conv's store."""
+
+    @staticmethod
+    def forward(ctx, fea, base, pcs, scale, w1, b1, w2, b2):
+        h, y = _leg_forward(fea, base, pcs, (w1, b1, w2, b2), scale, _lw())
+        out = y if scale == 4 else K.pixel_shuffle_base(y, base, scale, logical_w=_lw())
+        ctx.save_for_backward(fea, h)
+        ctx.pcs, ctx.scale = pcs, scale
+        ctx.wshape, ctx.wshape2 = tuple(w1.shape), tuple(w2.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        fea, h = ctx.saved_tensors
+        dout = dout.contiguous()
+        dyl = K.pixel_unshuffle4(dout) if ctx.scale == 4 else K.pixel_unshuffle(dout, ctx.scale, ctx.pcs[1].cout_pad)
+        dfea, *dparams = _leg_backward(ctx, fea, h, dyl)
+        # base comes from a parameter-free interpolation of the network input: no gradient
+        return (dfea, None, None, None) + tuple(dparams)
+
+
 class ExitFn(torch.autograd.Function):
     """One whole exit of the training step: LarvaLeg.forward followed by nn.L1Loss against the
     truth (models/LarvaNet.py:107-108).  Same kernels as LegFn + L1LossFn, but the backward
     writes the L1 gradient directly in the pixel-unshuffled layout the leg's dgrad/wgrad read
     (one fused launch instead of l1_bwd + pixel_unshuffle, no HR-layout gradient tensor).
-    Returns (exit image, loss term); the image output carries no gradient path of its own."""
+    Returns (exit image, loss term); the image output carries no gradient path of its own.  With a divisor the term
+    is the block partial sums of |out - truth| as they enter the mean over `divisor` exits, finished by MeanTermsFn
+    together with the other exits (see LossTerm); its gradient arrives unscaled and the 1/divisor is applied inside the
+    L1 backward kernel.  When the seed of backward is known (the plugin's step) the gradient is written in the same
+    pass as the partial sums, already unshuffled."""
 
     @staticmethod
-    def forward(ctx, fea, base, truth, pcs, w1, b1, w2, b2, divisor=None):
-        (f1, _), = pcs[0].get()
-        (f2, _), = pcs[1].get()
-        c = int(w1.shape[0])
-        h = K.conv3x3(fea, f1, c, bias=b1.detach(), relu=True)
-        out = K.conv3x3(h, f2, int(w2.shape[0]), bias=b2.detach(), shuffle=True, base=base)
+    def forward(ctx, fea, base, truth, pcs, scale, divisor, w1, b1, w2, b2):
+        h, y = _leg_forward(fea, base, pcs, (w1, b1, w2, b2), scale)
+        ctx.gscale = 1.0 if divisor is None else float(np.float32(1.0) / np.float32(divisor))
         dyl = None
-        if divisor is None:
-            term = K.l1_fwd(out, truth)   # the finished L1 value
-            ctx.gscale = 1.0
-        else:
-            # the term as it enters the mean over `divisor` exits: block partial sums of |out-truth|,
-            # finished by MeanTermsFn together with the other exits (see LossTerm); its gradient
-            # arrives unscaled and the 1/divisor is applied inside the L1 backward kernel
-            ctx.gscale = float(np.float32(1.0) / np.float32(divisor))
-            if StepScope.seed_grad is not None:  # gradient value known now: one sweep does both
+        fused = divisor is not None and StepScope.seed_grad is not None   # gradient value known now: one sweep does both
+        if scale == 4:
+            out = y
+            if fused:
                 term, _, dyl = K.l1_partial_grad(out, truth, StepScope.seed_grad, ctx.gscale)
-            else:
-                term, _ = K.l1_partial(out, truth)
-        ctx.have_dyl = dyl is not None
-        if dyl is not None:
-            ctx.save_for_backward(fea, h, dyl)
+        elif fused:
+            term, _, dyl, out = K.shuffle_l1_partial_grad(y, base, truth, StepScope.seed_grad, ctx.gscale, scale)
         else:
-            ctx.save_for_backward(fea, h, out, truth)
-        ctx.pcs = pcs
+            out = K.pixel_shuffle_base(y, base, scale)
+        if dyl is None:
+            term = K.l1_fwd(out, truth) if divisor is None else K.l1_partial(out, truth)[0]
+        ctx.have_dyl = dyl is not None
+        ctx.save_for_backward(fea, h, *((dyl,) if dyl is not None else (out, truth)))
+        ctx.pcs, ctx.scale = pcs, scale
         ctx.wshape, ctx.wshape2 = tuple(w1.shape), tuple(w2.shape)
         ctx.mark_non_differentiable(out)
         ctx.set_materialize_grads(False)  # no 7 MB zero gradient for the non-differentiable image output
@@ -864,29 +910,20 @@ class ExitFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, _dout, gterm):
-        if ctx.have_dyl:
-            fea, h, dyl = ctx.saved_tensors[:3]
-        else:
-            fea, h, out, truth = ctx.saved_tensors[:4]
-        pcs = ctx.pcs
-        c = ctx.wshape[0]
         if gterm is None:
-            return (None,) * 9
-        (_, bw1), = pcs[0].get()
-        (_, bw2), = pcs[1].get()
-        if not ctx.have_dyl:
+            return (None,) * 10
+        saved = ctx.saved_tensors
+        fea, h = saved[:2]
+        if ctx.have_dyl:
+            dyl = saved[2]
+        else:
             # (a partial-sum term receives its scalar gradient broadcast to its shape: element 0)
             g0 = gterm.as_strided((), ()) if gterm.dim() else gterm.contiguous()
-            dyl = K.l1_bwd_unshuffle4(out, truth, g0, ctx.gscale)
-        dh = K.conv3x3(dyl, bw2, c, mask=h)
-        dfea = K.conv3x3(dh, bw1, c)
-        ((dw1, db1),), ((dw2, db2),) = _leg_wgrad([(dh, fea, ctx.wshape, 0, c) + _targets(pcs[0])],
-                                                    [(dyl, h, ctx.wshape2, 0, c) + _targets(pcs[1])], c, ctx.wshape2[0])
-        if _targets(pcs[0])[0] is not None:
-            dw1 = db1 = None
-        if _targets(pcs[1])[0] is not None:
-            dw2 = db2 = None
-        return dfea, None, None, None, dw1, db1, dw2, db2, None
+            out, truth = saved[2:4]
+            dyl = K.l1_bwd_unshuffle4(out, truth, g0, ctx.gscale) if ctx.scale == 4 else \
+                K.l1_bwd_unshuffle(out, truth, g0, ctx.scale, ctx.pcs[1].cout_pad, ctx.gscale)
+        dfea, *dparams = _leg_backward(ctx, fea, h, dyl)
+        return (dfea, None, None, None, None, None) + tuple(dparams)
 
 
 def _conv_group(jobs, cout, **kw):

@@ -41,7 +41,8 @@ class HalfPack:
 
 
 class HalfForward:
-    """The fp16 forward of one LarvaNetModule (V1, V2, LarvaLeg, LarvaLegV2)."""
+    """The fp16 forward of one LarvaNetModule, along the module's own inference route (net.route(): how many bodies
+    run and the LarvaLeg / LarvaTail that ends them, or None = the base image alone)."""
 
     def __init__(self, net):
         self.net = net
@@ -49,19 +50,13 @@ class HalfForward:
         self._flag = None
 
     def _convs(self):
-        net = self.net
-        legs = getattr(net, "leg", None)
-        nb = net.len if legs is None else legs
+        bodies, end = self.net.route()
         out = []
-        for i in range(nb):
-            body = getattr(net, "body_%d" % i)
+        for body in self.net.bodies(bodies):
             for blk in body.res_blocks:
                 out += [blk.body[0], blk.body[2]]
-        if legs is None and hasattr(net, "tail"):
-            out += [net.tail.merge_conv, net.tail.recon_block[0], net.tail.recon_block[2]]
-        elif nb > 0:
-            rb = getattr(net, "body_%d" % (nb - 1)).leg.recon_block
-            out += [rb[0], rb[2]]
+        if end is not None:
+            out += ([end.merge_conv] if end.merges else []) + [end.recon_block[0], end.recon_block[2]]
         return out
 
     def _wpk(self, conv):
@@ -120,20 +115,18 @@ class HalfForward:
         """fp32 [N][3][H][W] -> the fp32 [N][3][4H][4W] image, or with u8 its uint8 [N][4H][4W][3] form
         (K.f32_chw_to_u8_hwc of the former, bit for bit)."""
         net = self.net
+        bodies, end = net.route()
         x = x.contiguous()
         base = net.base(x)
-        legs = getattr(net, "leg", None)
-        if legs == 0:
+        if end is None:
             return K.f32_chw_to_u8_hwc(base) if u8 else base
         flag = self.flag(x.device)
         head = net.head.feature_extraction
         fea = K.f16_head(x, head.weight.detach(), head.bias.detach(), flag)
-        nb = net.len if legs is None else legs
         feats = []
-        for i in range(nb):
-            fea = self._body(getattr(net, "body_%d" % i), fea, flag)
+        for body in net.bodies(bodies):
+            fea = self._body(body, fea, flag)
             feats.append(fea)
-        if legs is None and hasattr(net, "tail"):
-            fea = self._conv(net.tail.merge_conv, feats, flag)
-            return self._leg_end(net.tail.recon_block, fea, base, flag, u8)
-        return self._leg_end(getattr(net, "body_%d" % (nb - 1)).leg.recon_block, fea, base, flag, u8)
+        if end.merges:
+            fea = self._conv(end.merge_conv, feats, flag)
+        return self._leg_end(end.recon_block, fea, base, flag, u8)

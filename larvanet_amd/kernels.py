@@ -17,16 +17,29 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def _chk(t, name, shape=None):
+def _chk_tensor(t, name, shape, dtype, last=None):
+    """The checks every operand gets -> its device pointer.  float32 operands have any shape; `last` = the trailing
+    dimension of the 4-D channels-last formats (fp16 activations [N][H][W][48], uint8 images [N][H][W][3])."""
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise RuntimeError("larvanet_amd: %s must be a tensor on a HIP device (no CPU path exists)" % name)
-    if t.dtype != torch.float32:
-        raise RuntimeError("larvanet_amd: %s must be float32, got %s" % (name, t.dtype))
-    if not t.is_contiguous():
-        raise RuntimeError("larvanet_amd: %s must be contiguous" % name)
+    kind = str(dtype).replace("torch.", "")
+    if last is None:
+        if t.dtype != dtype:
+            raise RuntimeError("larvanet_amd: %s must be %s, got %s" % (name, kind, t.dtype))
+        if not t.is_contiguous():
+            raise RuntimeError("larvanet_amd: %s must be contiguous" % name)
+    else:
+        if t.dtype != dtype or not t.is_contiguous():
+            raise RuntimeError("larvanet_amd: %s must be a contiguous %s tensor, got %s" % (name, kind, t.dtype))
+        if t.dim() != 4 or int(t.shape[3]) != last:
+            raise RuntimeError("larvanet_amd: %s must be [N][H][W][%d], got %s" % (name, last, tuple(t.shape)))
     if shape is not None and tuple(t.shape) != tuple(shape):
         raise RuntimeError("larvanet_amd: %s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
     return t.data_ptr()
+
+
+def _chk(t, name, shape=None):
+    return _chk_tensor(t, name, shape, torch.float32)
 
 
 def _opt(t, name, shape):
@@ -64,27 +77,32 @@ def pack_weights(w, cin_off=0, cin=None, cin_pad=None, want_bwd=True):
     return fwd, bwd
 
 
+def _pack_job_args(jobs):
+    """Pack jobs (w, fwd_buf, bwd_buf or None, cout, cin_k, cin_off), checked -> the leading arguments of
+    larva_pack_weights_batch / larva_step_prologue: weights, forward and backward images, cout, cin_k, cin_total,
+    cin_off per job, and the job count."""
+    ws, fs, bs, couts, cins, totals, offs = [], [], [], [], [], [], []
+    for (w, fwd, bwd, cout, cin_k, cin_off) in jobs:
+        _chk(w, "w")
+        if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or int(w.shape[0]) != cout:
+            raise RuntimeError("larvanet_amd: only [cout][cin][3][3] weights are supported")
+        ws.append(w.data_ptr())
+        fs.append(_chk(fwd, "wpk_fwd", (packed_weight_floats(cout, cin_k),)))
+        bs.append(None if bwd is None else _chk(bwd, "wpk_bwd", (packed_weight_floats(cin_k, cout),)))
+        couts.append(cout)
+        cins.append(cin_k)
+        totals.append(int(w.shape[1]))
+        offs.append(cin_off)
+    return (hip_lib.ptr_array(ws), hip_lib.ptr_array(fs), hip_lib.ptr_array(bs), hip_lib.int_array(couts),
+            hip_lib.int_array(cins), hip_lib.int_array(totals), hip_lib.int_array(offs), len(jobs))
+
+
 def pack_weights_batch(jobs):
     """jobs: list of (w, fwd_buf, bwd_buf or None, cout, cin_k, cin_off): packs every weight
     (slice) into its persistent kernel-layout buffers with one launch per 64 jobs."""
     lib = hip_lib.load()
     for i in range(0, len(jobs), 64):
-        chunk = jobs[i:i + 64]
-        ws, fs, bs, couts, cins, totals, offs = [], [], [], [], [], [], []
-        for (w, fwd, bwd, cout, cin_k, cin_off) in chunk:
-            _chk(w, "w")
-            if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or int(w.shape[0]) != cout:
-                raise RuntimeError("larvanet_amd: only [cout][cin][3][3] weights are supported")
-            ws.append(w.data_ptr())
-            fs.append(_chk(fwd, "wpk_fwd", (packed_weight_floats(cout, cin_k),)))
-            bs.append(None if bwd is None else _chk(bwd, "wpk_bwd", (packed_weight_floats(cin_k, cout),)))
-            couts.append(cout)
-            cins.append(cin_k)
-            totals.append(int(w.shape[1]))
-            offs.append(cin_off)
-        code = lib.larva_pack_weights_batch(hip_lib.ptr_array(ws), hip_lib.ptr_array(fs), hip_lib.ptr_array(bs),
-                                            hip_lib.int_array(couts), hip_lib.int_array(cins),
-                                            hip_lib.int_array(totals), hip_lib.int_array(offs), len(chunk), _stream())
+        code = lib.larva_pack_weights_batch(*_pack_job_args(jobs[i:i + 64]), _stream())
         hip_lib.check(code, "larva_pack_weights_batch")
 
 
@@ -125,20 +143,7 @@ def step_prologue(jobs, x, x16, base):
     _chk(x, "x")
     _chk(x16, "x16", (N, 16, H, W))
     _chk(base, "base", (N, C, 4 * H, 4 * W))
-    ws, fs, bs, couts, cins, totals, offs = [], [], [], [], [], [], []
-    for (w, fwd, bwd, cout, cin_k, cin_off) in jobs:
-        _chk(w, "w")
-        ws.append(w.data_ptr())
-        fs.append(_chk(fwd, "wpk_fwd", (packed_weight_floats(cout, cin_k),)))
-        bs.append(None if bwd is None else _chk(bwd, "wpk_bwd", (packed_weight_floats(cin_k, cout),)))
-        couts.append(cout)
-        cins.append(cin_k)
-        totals.append(int(w.shape[1]))
-        offs.append(cin_off)
-    code = lib.larva_step_prologue(hip_lib.ptr_array(ws), hip_lib.ptr_array(fs), hip_lib.ptr_array(bs),
-                                   hip_lib.int_array(couts), hip_lib.int_array(cins), hip_lib.int_array(totals),
-                                   hip_lib.int_array(offs), len(jobs), x.data_ptr(), x16.data_ptr(), base.data_ptr(),
-                                   N, C, H, W, _stream())
+    code = lib.larva_step_prologue(*_pack_job_args(jobs), x.data_ptr(), x16.data_ptr(), base.data_ptr(), N, C, H, W, _stream())
     hip_lib.check(code, "larva_step_prologue")
 
 
@@ -729,17 +734,9 @@ def loss_from_partials(terms, scales, divisor, host_cell=None):
     lib = hip_lib.load()
     if not 1 <= len(terms) <= 8:
         raise RuntimeError("larvanet_amd: 1..8 loss terms")
-    ptrs, counts = [], []
-    for t in terms:
-        _chk(t, "term")
-        if t.dim() > 1:
-            raise RuntimeError("larvanet_amd: a loss term is a scalar or a vector of partial sums")
-        ptrs.append(t.data_ptr())
-        counts.append(max(1, int(t.numel())))
     out = torch.empty((), device=terms[0].device, dtype=torch.float32)
-    sc = (ctypes.c_float * len(terms))(*[float(v) for v in scales])
     hip_lib.check(lib.larva_loss_from_partials_to_host_seq(
-        hip_lib.ptr_array(ptrs), hip_lib.int_array(counts), sc, len(terms), float(divisor), out.data_ptr(),
+        *_loss_terms(terms, scales), len(terms), float(divisor), out.data_ptr(),
         host_cell.ptr if host_cell is not None else None,
         host_cell.dev_seq.data_ptr() if host_cell is not None and host_cell.dev_seq is not None else None, _stream()),
         "larva_loss_from_partials_to_host")
@@ -872,15 +869,13 @@ F16_MAX_SOURCES = 8
 
 def _chk16(t, name, shape=None):
     """An fp16 channels-last activation [N][H][W][48] (torch.float16, contiguous, on the device)."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("larvanet_amd: %s must be a tensor on a HIP device (no CPU path exists)" % name)
-    if t.dtype != torch.float16 or not t.is_contiguous():
-        raise RuntimeError("larvanet_amd: %s must be a contiguous float16 tensor, got %s" % (name, t.dtype))
-    if t.dim() != 4 or int(t.shape[3]) != F16_CHANNELS:
-        raise RuntimeError("larvanet_amd: %s must be [N][H][W][%d], got %s" % (name, F16_CHANNELS, tuple(t.shape)))
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise RuntimeError("larvanet_amd: %s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
-    return t.data_ptr()
+    return _chk_tensor(t, name, shape, torch.float16, F16_CHANNELS)
+
+
+def _chk_wpk16(wpk, n_src, what):
+    """wpk is the fp16 A-operand image of a conv over n_src 48-channel inputs (f16_pack_weights)."""
+    if wpk.dtype != torch.float16 or not wpk.is_cuda or wpk.numel() != f16_packed_weight_halves(F16_CHANNELS, F16_CHANNELS * n_src):
+        raise RuntimeError("larvanet_amd: wpk is not the fp16 image of a %s conv" % what)
 
 
 def _chk_flag(flag):
@@ -939,8 +934,7 @@ def f16_conv3x3(srcs, wpk, bias, flag, relu=False, res0=None, res1=None, out=Non
     shape = tuple(srcs[0].shape)
     ptrs = [_chk16(s, "srcs[%d]" % i, shape) for i, s in enumerate(srcs)]
     N, H, W = shape[:3]
-    if wpk.dtype != torch.float16 or not wpk.is_cuda or wpk.numel() != f16_packed_weight_halves(F16_CHANNELS, F16_CHANNELS * len(srcs)):
-        raise RuntimeError("larvanet_amd: wpk is not the fp16 image of a %d-input conv" % len(srcs))
+    _chk_wpk16(wpk, len(srcs), "%d-input" % len(srcs))
     _chk(bias, "bias", (F16_CHANNELS,))
     if relu and res0 is not None:
         raise RuntimeError("larvanet_amd: the fp16 conv has no ReLU + residual epilogue")
@@ -962,8 +956,7 @@ def f16_conv3x3_shuffle_base(src, wpk, bias, base):
     lib = hip_lib.load()
     _chk16(src, "src")
     N, H, W = (int(v) for v in src.shape[:3])
-    if wpk.dtype != torch.float16 or not wpk.is_cuda or wpk.numel() != f16_packed_weight_halves(F16_CHANNELS, F16_CHANNELS):
-        raise RuntimeError("larvanet_amd: wpk is not the fp16 image of a 48 -> 48 conv")
+    _chk_wpk16(wpk, 1, "48 -> 48")
     _chk(bias, "bias", (F16_CHANNELS,))
     hr = (N, 3, 4 * H, 4 * W)
     _chk(base, "base", hr)
@@ -979,8 +972,7 @@ def f16_conv3x3_shuffle_base_u8(src, wpk, bias, base, flag, out=None):
     lib = hip_lib.load()
     _chk16(src, "src")
     N, H, W = (int(v) for v in src.shape[:3])
-    if wpk.dtype != torch.float16 or not wpk.is_cuda or wpk.numel() != f16_packed_weight_halves(F16_CHANNELS, F16_CHANNELS):
-        raise RuntimeError("larvanet_amd: wpk is not the fp16 image of a 48 -> 48 conv")
+    _chk_wpk16(wpk, 1, "48 -> 48")
     _chk(bias, "bias", (F16_CHANNELS,))
     _chk(base, "base", (N, 3, 4 * H, 4 * W))
     if out is None:
@@ -995,15 +987,7 @@ def f16_conv3x3_shuffle_base_u8(src, wpk, bias, base, flag, out=None):
 # ------------------------------------------------------------------ 8-bit images (csrc/larva_pointwise.hip)
 def _chk_u8(t, name, shape=None):
     """A uint8 image batch [N][H][W][3] (torch.uint8, contiguous, on the device)."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("larvanet_amd: %s must be a tensor on a HIP device (no CPU path exists)" % name)
-    if t.dtype != torch.uint8 or not t.is_contiguous():
-        raise RuntimeError("larvanet_amd: %s must be a contiguous uint8 tensor, got %s" % (name, t.dtype))
-    if t.dim() != 4 or int(t.shape[3]) != 3:
-        raise RuntimeError("larvanet_amd: %s must be [N][H][W][3], got %s" % (name, tuple(t.shape)))
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise RuntimeError("larvanet_amd: %s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
-    return t.data_ptr()
+    return _chk_tensor(t, name, shape, torch.uint8, 3)
 
 
 def u8_hwc_to_f32_chw(x, out=None):

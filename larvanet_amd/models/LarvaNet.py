@@ -24,7 +24,6 @@ from ..autograd import (BodyFn, DualChain, ExitFn, ExitsFn, GradBucket, HeadFn, 
                         StepScope, is_large_inference, pack_all)
 from ..autograd import step_prologue as autograd_step_prologue
 from ..optim import FlatAdamW, flatten_parameters
-from ..scaled import ScaledExitFn, ScaledLegFn
 from ..metrics import image_psnr, image_to_uint8, fit_truth_image_size
 from .base import BaseModel
 
@@ -42,7 +41,7 @@ NUM_FILTERS = 48  # = 3 * 4**2: PixelShuffle(4) of the leg output must give RGB 
 # reference counterpart and are checked against oracle/larva_torch.py only.
 SUPPORTED_NUM_FILTERS = (32, 48, 64)
 # prepare(scales=[s]), s = 2 / 3: the legs' last conv has 3 * s**2 = 12 / 27 outputs (PixelShuffle(s) gives RGB) and runs
-# as a 32-output conv on zero-padded weight rows (larvanet_amd/scaled.py).  Those ends exist for the reference's width
+# as a 32-output conv on zero-padded weight rows (autograd._leg_forward).  Those ends exist for the reference's width
 # only: --num_filters 32 / 64 at x2 / x3 is refused by prepare().
 SCALED_COUT_PAD = 32
 # --precision (build-side extension): fp16 runs the grad-free inference entry points (upscale, upscale_tensor, test,
@@ -139,15 +138,27 @@ class LarvaLeg(nn.Module):
                      PackedConv(self.recon_block[2].weight, self.recon_block[2].bias,
                                 cout_pad=None if scale == 4 else SCALED_COUT_PAD)]
 
+    merges = False   # (LarvaNetModule.forward: this end reads the last body's output, not every body's)
+
     def forward(self, fea, base):
         _require_hip(fea)
-        c1, c2 = self.recon_block[0], self.recon_block[2]
-        for pc in self._pcs:
-            pc.refresh()
-        if self.scale != 4:
-            return ScaledLegFn.apply(fea.contiguous(), base.contiguous(), self._pcs, self.scale, c1.weight, c1.bias,
-                                     c2.weight, c2.bias)
-        return LegFn.apply(fea.contiguous(), base.contiguous(), self._pcs, c1.weight, c1.bias, c2.weight, c2.bias)
+        return run_leg(self, fea, base)
+
+
+def run_leg(end, fea, base, truth=None, divisor=None):
+    """Refresh the two PackedConvs of `end` (a LarvaLeg or the V2 LarvaTail) and apply its conv + ReLU, conv ->
+    PixelShuffle(scale) -> + base to `fea`: the image (LegFn) or, given the truth, one fused training exit (ExitFn) ->
+    (image, loss term).  An end that merges (the tail) is handed every body's output and runs its merge conv on them
+    first, after the refresh."""
+    for pc in end._pcs:
+        pc.refresh()
+    if end.merges:
+        fea = end.merge(fea)
+    c1, c2 = end.recon_block[0], end.recon_block[2]
+    params = (c1.weight, c1.bias, c2.weight, c2.bias)
+    if truth is None:
+        return LegFn.apply(fea.contiguous(), base.contiguous(), end._pcs, end.scale, *params)
+    return ExitFn.apply(fea.contiguous(), base.contiguous(), truth.contiguous(), end._pcs, end.scale, divisor, *params)
 
 
 class LarvaBody(nn.Module):
@@ -262,14 +273,29 @@ class LarvaNetModule(nn.Module):
             return PaddedWidth(w)
         return _NoScope()
 
+    def bodies(self, n):
+        return [getattr(self, "body_%d" % i) for i in range(n)]
+
+    def route(self):
+        """The inference route, stated once per module class: (how many bodies run, what ends it) -- the end is a
+        LarvaLeg, the V2 LarvaTail, or None = the base image alone.  forward() and the fp16 forward (half.HalfForward)
+        both walk it."""
+        return self.len, getattr(self, "body_%d" % (self.len - 1)).leg
+
     def forward(self, x):
+        bodies, end = self.route()
+        base = self.base(x)
+        if end is None:
+            return base
         with self.width_scope(x):
-            base = self.base(x)
             fea = self.head(x)
-            for i in range(self.len):
-                fea = getattr(self, "body_%d" % i)(fea)
+            feats = []
+            for body in self.bodies(bodies):
+                fea = body(fea)
+                if end.merges:   # (only the tail reads every body's output: a leg lets the earlier ones go)
+                    feats.append(fea)
             DualChain.join()   # (no-op unless the layer chain ran as two half-batch chains)
-            return getattr(self, "body_%d" % (self.len - 1)).leg(fea, base)
+            return end(feats if end.merges else fea, base)
 
 
 class LarvaNet(BaseModel):
@@ -309,6 +335,8 @@ class LarvaNet(BaseModel):
         self.force_split_backward = os.environ.get("LARVA_FORCE_SPLIT", "0") != "0"
 
     # ------------------------------------------------------------------ flags
+    has_cooldown = True   # this flag set has --cooldown (V2's, which LarvaLeg / LarvaLegV2 share, does not)
+
     def _add_args(self, parser):
         parser.add_argument("--num_modules", type=int, default=2, help="Number of cascaded bodies (exits).")
         # the reference declares type=str with an int default, which cannot be split (models/LarvaNet.py:51,276)
@@ -347,8 +375,8 @@ class LarvaNet(BaseModel):
     def _make_scheduler(self):
         return torch.optim.lr_scheduler.ReduceLROnPlateau(
             self.optim, mode="max", factor=self.args.lr_decay, patience=self.args.patience,
-            cooldown=self.args.cooldown, threshold=self.args.threshold, threshold_mode="abs",
-            min_lr=self.args.min_lr)
+            cooldown=self.args.cooldown if self.has_cooldown else 0,
+            threshold=self.args.threshold, threshold_mode="abs", min_lr=self.args.min_lr)
 
     def prepare(self, is_training, scales, global_step=0):
         self.global_step = global_step
@@ -449,19 +477,8 @@ class LarvaNet(BaseModel):
         the stock L1Loss; otherwise the two separate calls of the reference.  Returns (image, term):
         in the fused case the term is a LossTerm of partial sums that the mean over the exits
         finishes (no per-exit finishing launch, the 1/M of the mean applied inside L1's backward)."""
-        if isinstance(self.loss_fn, L1Loss) and isinstance(leg, LarvaLeg) and leg.scale != 4:
-            for pc in leg._pcs:
-                pc.refresh()
-            c1, c2 = leg.recon_block[0], leg.recon_block[2]
-            out, part = ScaledExitFn.apply(fea.contiguous(), base.contiguous(), truth_tensor.contiguous(), leg._pcs, leg.scale,
-                                           self._num_loss_terms(), c1.weight, c1.bias, c2.weight, c2.bias)
-            return out, LossTerm(part, 1.0 / float(out.numel()), prescaled=True)
         if isinstance(self.loss_fn, L1Loss) and isinstance(leg, LarvaLeg):
-            for pc in leg._pcs:
-                pc.refresh()
-            c1, c2 = leg.recon_block[0], leg.recon_block[2]
-            out, part = ExitFn.apply(fea.contiguous(), base.contiguous(), truth_tensor.contiguous(), leg._pcs,
-                                     c1.weight, c1.bias, c2.weight, c2.bias, self._num_loss_terms())
+            out, part = run_leg(leg, fea, base, truth_tensor, self._num_loss_terms())
             return out, LossTerm(part, 1.0 / float(out.numel()), prescaled=True)
         out = leg(fea, base)
         return out, self.loss_fn(out, truth_tensor)
@@ -470,7 +487,7 @@ class LarvaNet(BaseModel):
         """All exits as one autograd node with batched launches (ExitsFn): the stock L1 loss on
         stock legs, training-shaped input (no row pitch)."""
         return (self.batch_exits and isinstance(self.loss_fn, L1Loss) and PaddedWidth.current is None
-                and self.model.scale == 4   # (x2 / x3: one ScaledExitFn per exit)
+                and self.model.scale == 4   # (x2 / x3: one ExitFn per exit)
                 and all(isinstance(getattr(self.model, "body_%d" % i).leg, LarvaLeg) for i in range(self.args.num_modules)))
 
     def _all_exits(self, feas, base, truth_tensor):
@@ -878,34 +895,40 @@ class LarvaNet(BaseModel):
         # 339 x 510 image (tools/infer_modes.py, round 5).  The capture pays where the launches are short.
         if is_large_inference(x.shape[0], x.shape[2], x.shape[3]):   # (the same rule picks the direct head kernel)
             return self._forward_nograd(x)
-        cache = self.__dict__.setdefault("_infer_graphs", {})
-        seen = self.__dict__.setdefault("_infer_seen", {})
-        key = (tuple(x.shape), self._precision())
+        return self._capture_or_run(x, False)
+
+    def _infer_u8(self, x_u8):
+        """_infer for the uint8 path [N][H][W][3], with the same rules.  Its graphs are kept under (shape, precision,
+        "u8") in a table of their own (_infer_graphs_u8, with its own limit of four), so the float path captures exactly
+        what it would without this one.  A replay returns the graph's output buffer."""
+        if not self.use_hip_graph or is_large_inference(x_u8.shape[0], x_u8.shape[1], x_u8.shape[2]):
+            return self._forward_nograd(x_u8, True)
+        return self._capture_or_run(x_u8, True)
+
+    def _capture_or_run(self, x, u8):
+        """The grad-free forward of a small device batch `x` (uint8 images when u8): a shape seen once runs eagerly; seen
+        for the second time it is captured (at most four graphs per table; False marks a capture that failed) and
+        replayed from then on."""
+        cache = self.__dict__.setdefault("_infer_graphs_u8" if u8 else "_infer_graphs", {})
+        seen = self.__dict__.setdefault("_infer_seen_u8" if u8 else "_infer_seen", {})
+        key = (tuple(x.shape), self._precision()) + (("u8",) if u8 else ())
         ent = cache.get(key)
         if ent is None:
             if len(seen) > 512:   # (a long run over images of ever new sizes: forget the counts)
                 seen.clear()
             seen[key] = seen.get(key, 0) + 1
             if seen[key] < 2 or len(cache) >= 4:
-                return self._forward_nograd(x)
-            ent = cache[key] = self._capture_infer(x)
-            if ent is False:
-                return self._forward_nograd(x)
+                return self._forward_nograd(x, u8)
+            ent = cache[key] = self._capture_infer(x, u8)
         if ent is False:
-            return self._forward_nograd(x)
-        # weights restored / stepped since the capture: repack (outside the graph)
-        if self._precision() == "fp16":
-            self.model.half_forward().refresh()
-        else:
-            for pc in self.model.packed_convs():
-                pc.refresh()
+            return self._forward_nograd(x, u8)
+        self._refresh_inference_weights()   # weights restored / stepped since the capture: repack (outside the graph)
         static_x, graph, out = ent
         static_x.copy_(x)
         graph.replay()
         return out
 
-    def _capture_infer(self, x, forward=None):
-        forward = forward or self._forward_nograd
+    def _capture_infer(self, x, u8=False):
         static_x = x.clone()
         try:
             side = torch.cuda.Stream()
@@ -913,12 +936,12 @@ class LarvaNet(BaseModel):
             with torch.cuda.stream(side):
                 for _ in range(2):
                     with self._infer_scope():
-                        forward(static_x)
+                        self._forward_nograd(static_x, u8)
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
                 with self._infer_scope():
-                    out = forward(static_x)
+                    out = self._forward_nograd(static_x, u8)
             return static_x, graph, out
         except Exception as e:   # an optimisation only
             if self.strict_graph:
@@ -931,31 +954,56 @@ class LarvaNet(BaseModel):
     def _precision(self):
         return getattr(self, "precision", "fp32")
 
-    def _forward_nograd(self, x):
-        """The inference forward at the model's precision (no graph)."""
-        if self._precision() == "fp16":
-            return self.model.half_forward()(x)
-        return self.model(x)
+    def _half(self):
+        """The fp16 forward when the model runs at --precision fp16, else None: the one place precision is decided."""
+        return self.model.half_forward() if self._precision() == "fp16" else None
 
-    def _clear_overflow(self):
-        if self._precision() == "fp16":
-            self.model.half_forward().clear_overflow()
+    def _forward_nograd(self, x, u8=False):
+        """The inference forward at the model's precision (no graph).  u8: uint8 [N][H][W][3] -> uint8 [N][sH][sW][3],
+        the float forward over the exactly converted image, then round half to even + clamp on the device (at fp16 the
+        leg end's epilogue stores the bytes itself)."""
+        half = self._half()
+        if u8:
+            x = K.u8_hwc_to_f32_chw(x)
+        if half is not None:
+            return half(x, u8=u8)
+        out = self.model(x)
+        return K.f32_chw_to_u8_hwc(out.contiguous()) if u8 else out
 
-    def _check_overflow(self):
-        """upscale / upscale_tensor / test: an fp16 activation that left the fp16 range is an error, not a result."""
-        if self._precision() == "fp16" and self.model.half_forward().take_overflow():
-            raise FloatingPointError("larvanet_amd: an activation exceeded the fp16 range (|v| > 65504 or not finite) "
-                                     "under --precision fp16; run this model with --precision fp32")
+    def _refresh_inference_weights(self):
+        """Repack the stale weight images of the active precision."""
+        half = self._half()
+        if half is not None:
+            half.refresh()
+        else:
+            for pc in self.model.packed_convs():
+                pc.refresh()
+
+    def overflow_flag(self):
+        """The device flag the fp16 launches set on overflow (int32 [1]), or None at --precision fp32."""
+        half = self._half()
+        return None if half is None else half.flag(self.device)
+
+    @staticmethod
+    def overflow_error():
+        return FloatingPointError("larvanet_amd: an activation exceeded the fp16 range (|v| > 65504 or not finite) "
+                                  "under --precision fp16; run this model with --precision fp32")
 
     def fp16_overflowed(self):
         """True if an fp16 inference forward (fwd_runtime included) overflowed since the last check; clears the flag.
         Always False at --precision fp32."""
-        return self._precision() == "fp16" and self.model.half_forward().take_overflow()
+        half = self._half()
+        return half is not None and half.take_overflow()
 
-    def _infer_checked(self, x):
-        self._clear_overflow()
-        out = self._infer(x)
-        self._check_overflow()
+    def _infer_checked(self, x, u8=False):
+        """upscale / upscale_tensor / test and their uint8 forms: an fp16 activation that left the fp16 range is an
+        error, not a result."""
+        half = self._half()
+        if half is not None:
+            half.clear_overflow()
+        out = self._infer_u8(x) if u8 else self._infer(x)
+        if self.fp16_overflowed():
+            raise self.overflow_error()
         return out
 
     def _to_input_tensor(self, input_list):
@@ -973,44 +1021,6 @@ class LarvaNet(BaseModel):
             return self._infer_checked(self._to_input_tensor(input_list)).detach().clone()
 
     # ------------------------------------------------------------------ 8-bit images in, 8-bit images out
-    def _forward_nograd_u8(self, x_u8):
-        """uint8 [N][H][W][3] -> uint8 [N][sH][sW][3] (no graph): the float forward over the exactly converted image,
-        then round half to even + clamp on the device.  At fp16 the leg end's epilogue stores the bytes itself."""
-        x = K.u8_hwc_to_f32_chw(x_u8)
-        if self._precision() == "fp16":
-            return self.model.half_forward()(x, u8=True)
-        return K.f32_chw_to_u8_hwc(self.model(x).contiguous())
-
-    def _infer_u8(self, x_u8):
-        """_infer for the uint8 path, with the same rules (second sight of a shape captures, large images run
-        eagerly).  Its graphs are kept under (shape, precision, "u8") in a table of their own (_infer_graphs_u8, with
-        its own limit of four), so the float path captures exactly what it did without this one.  A replay returns the
-        graph's output buffer."""
-        if not self.use_hip_graph or is_large_inference(x_u8.shape[0], x_u8.shape[1], x_u8.shape[2]):
-            return self._forward_nograd_u8(x_u8)
-        cache = self.__dict__.setdefault("_infer_graphs_u8", {})
-        seen = self.__dict__.setdefault("_infer_seen_u8", {})
-        key = (tuple(x_u8.shape), self._precision(), "u8")
-        ent = cache.get(key)
-        if ent is None:
-            if len(seen) > 512:
-                seen.clear()
-            seen[key] = seen.get(key, 0) + 1
-            if seen[key] < 2 or len(cache) >= 4:
-                return self._forward_nograd_u8(x_u8)
-            ent = cache[key] = self._capture_infer(x_u8, self._forward_nograd_u8)
-        if ent is False:
-            return self._forward_nograd_u8(x_u8)
-        if self._precision() == "fp16":
-            self.model.half_forward().refresh()
-        else:
-            for pc in self.model.packed_convs():
-                pc.refresh()
-        static_x, graph, out = ent
-        static_x.copy_(x_u8)
-        graph.replay()
-        return out
-
     def _check_u8_images(self, input_list, scale):
         """Host-side argument checks of upscale_u8 (before any device work) -> the (N, H, W, 3) uint8 batch."""
         if int(scale) != self.scale:
@@ -1037,12 +1047,6 @@ class LarvaNet(BaseModel):
         _require_hip(x_u8)
         return x_u8.contiguous()
 
-    def _infer_u8_checked(self, x_u8):
-        self._clear_overflow()
-        out = self._infer_u8(x_u8)
-        self._check_overflow()
-        return out
-
     def upscale_u8(self, input_list, scale):
         """list of uint8 (H, W, 3) images of one shape -> uint8 (N, sH, sW, 3) numpy:
         image_to_uint8(upscale(...)) byte for byte, transposed for an image writer, with a quarter of the bytes crossing
@@ -1051,13 +1055,13 @@ class LarvaNet(BaseModel):
         with torch.no_grad():
             x = torch.from_numpy(batch).to(self.device)
             _require_hip(x)
-            return self._infer_u8_checked(x).cpu().numpy()
+            return self._infer_checked(x, u8=True).cpu().numpy()
 
     def upscale_u8_tensor(self, x_u8):
         """upscale_u8 without the trips to and from the host: uint8 [N][H][W][3] on self.device -> uint8 [N][sH][sW][3]."""
         x = self._check_u8_tensor(x_u8)
         with torch.no_grad():
-            return self._infer_u8_checked(x).clone()
+            return self._infer_checked(x, u8=True).clone()
 
     def receptive_halo(self):
         """LR pixels beyond an output pixel's own LR pixel that can influence it: one per 3x3

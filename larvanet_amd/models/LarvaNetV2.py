@@ -11,10 +11,9 @@ state_dict adds tail.merge_conv.{weight,bias} and tail.recon_block.{0,2}.{weight
 import torch
 import torch.nn as nn
 
-from ..autograd import DualChain, LegFn, MergeFn, PackedConv, mean_of_terms
-from ..scaled import ScaledLegFn
+from ..autograd import DualChain, MergeFn, PackedConv, mean_of_terms
 from . import LarvaNet as V1
-from .LarvaNet import NUM_FILTERS, _conv, _require_hip, init_conv
+from .LarvaNet import NUM_FILTERS, _conv, _require_hip, init_conv, run_leg
 
 
 def create_model():
@@ -41,17 +40,16 @@ class LarvaTail(nn.Module):
                      PackedConv(self.recon_block[2].weight, self.recon_block[2].bias,
                                 cout_pad=None if scale == 4 else V1.SCALED_COUT_PAD)]
 
+    merges = True   # (LarvaNetModule.forward: this end reads every body's output)
+
+    def merge(self, features):
+        m = self.merge_conv
+        return MergeFn.apply(self._pc, m.weight, m.bias, *[f.contiguous() for f in features])
+
     def forward(self, features, base):
         _require_hip(features[0])
         self._pc.refresh()
-        for pc in self._pcs:
-            pc.refresh()
-        m = self.merge_conv
-        fea = MergeFn.apply(self._pc, m.weight, m.bias, *[f.contiguous() for f in features])
-        c1, c2 = self.recon_block[0], self.recon_block[2]
-        if self.scale != 4:
-            return ScaledLegFn.apply(fea, base.contiguous(), self._pcs, self.scale, c1.weight, c1.bias, c2.weight, c2.bias)
-        return LegFn.apply(fea, base.contiguous(), self._pcs, c1.weight, c1.bias, c2.weight, c2.bias)
+        return run_leg(self, features, base)
 
 
 class LarvaNetModule(V1.LarvaNetModule):
@@ -61,26 +59,15 @@ class LarvaNetModule(V1.LarvaNetModule):
         super().__init__(args)
         self.tail = LarvaTail(self.len, self.num_filters, self.scale)
 
-    def features(self, x):
-        fea = self.head(x)
-        feats = []
-        for i in range(self.len):
-            fea = getattr(self, "body_%d" % i)(fea)
-            feats.append(fea)
-        return feats
-
-    def forward(self, x):
-        with self.width_scope(x):
-            base = self.base(x)
-            feats = self.features(x)
-            DualChain.join()
-            return self.tail(feats, base)
+    def route(self):
+        return self.len, self.tail
 
 
 class LarvaNet(V1.LarvaNet):
     """Plugin wrapper; control flow of models/LarvaNetV2.py:41-212."""
 
     module_class = LarvaNetModule
+    has_cooldown = False
 
     def _add_args(self, parser):
         # V2's flag set and defaults (models/LarvaNetV2.py:46-60): no --lr_step / --cooldown
@@ -94,11 +81,6 @@ class LarvaNet(V1.LarvaNet):
         parser.add_argument("--min_lr", type=float, default=1e-7)
         parser.add_argument("--patience", type=int, default=3)
         self._add_build_args(parser)
-
-    def _make_scheduler(self):
-        return torch.optim.lr_scheduler.ReduceLROnPlateau(
-            self.optim, mode="max", factor=self.args.lr_decay, patience=self.args.patience,
-            threshold=self.args.threshold, threshold_mode="abs", min_lr=self.args.min_lr)
 
     def _num_loss_terms(self):
         return self.args.num_modules + 1

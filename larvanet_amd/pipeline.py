@@ -83,12 +83,12 @@ def upscale_stream(model, images, scale, depth=2):
 
 
 def _stream(model, images, depth):
-    fp16 = model._precision() == "fp16"
     compute = torch.cuda.current_stream()
     copy = torch.cuda.Stream()
     free = [_Slot(model.device, copy) for _ in range(depth)]
     inflight = collections.deque()
-    model_flag = model.model.half_forward().flag(model.device) if fp16 else None
+    model_flag = model.overflow_flag()   # the fp16 launches' overflow flag; None at fp32
+    fp16 = model_flag is not None
 
     def issue_d2h(slot):
         if slot.d2h_issued:
@@ -106,8 +106,7 @@ def _stream(model, images, depth):
         issue_d2h(slot)
         slot.done.synchronize()
         if fp16 and int(slot.pin_flag[0]):
-            raise FloatingPointError("larvanet_amd: an activation exceeded the fp16 range (|v| > 65504 or not finite) "
-                                     "under --precision fp16; run this model with --precision fp32")
+            raise model.overflow_error()
         out = np.array(slot.views_out(slot.out_shape)[0].numpy()[0])
         free.append(slot)
         return out

@@ -222,7 +222,7 @@ def test_leg_conv2_shuffle_l1_and_unshuffled_gradient(hip_device, s):
         dh = K.conv3x3(grad, bwd, 48, mask=hd).cpu().numpy()
         dref = R.conv3x3_dgrad(gref, w.numpy()) * (h > 0)
         np.testing.assert_allclose(dh, dref, rtol=1e-4, atol=1e-4 * float(np.abs(dref).max()))
-        from larvanet_amd.scaled import padded_wgrad
+        from larvanet_amd.autograd import padded_wgrad
         pc.grad_inplace = False
         dw, db = padded_wgrad(grad, hd, pc, tuple(w.shape))
         dw_ref, db_ref = R.conv3x3_wgrad(gref, h)
