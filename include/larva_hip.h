@@ -336,6 +336,23 @@ int larva_sqerr_u8(const float* out, const unsigned char* truth, int C, int H, i
 int larva_u8_hwc_to_f32_chw(const unsigned char* in, float* out, int N, int H, int W, void* stream);
 int larva_f32_chw_to_u8_hwc(const float* in, unsigned char* out, int N, int H, int W, void* stream);
 
+/* ---- benchmark metrics of two uint8 HWC images (csrc/larva_metrics.hip) ------------------------------
+ * out, truth: uint8 [rows][pitch bytes], pixel (y, x) at y * pitch + 3 x.  The window is rows [y0, y0 + h) and columns
+ * [x0, x0 + w) of BOTH images (1 <= h, w <= 32768; pitch >= 3 (x0 + w); the caller guarantees the rows exist).  mode 0:
+ * the three colour planes; mode 1: the BT.601 luma plane, Y = 16 + round_half_even((65481 R + 128553 G + 24966 B) /
+ * 255000) in integers.  result (8 x 8 bytes, device memory, written by a final one-workgroup launch):
+ *   [0] uint64  sum of squared differences over the window and the mode's planes (exact)
+ *   [1..3] double  sum of the SSIM samples per plane (0 for unused planes or want_ssim == 0)
+ *   [4] int64  SSIM samples per plane = (h - 10) (w - 10), 0 without SSIM   [5] int64 h w planes   [6] int64 planes
+ * SSIM: 11-tap normalised Gaussian (sigma 1.5) over x, y, x^2, y^2, x y in double, K1 0.01, K2 0.03, range 255,
+ * population covariance, samples = the window minus 5 pixels on every side (needs h, w >= 11).  All sums are taken in a
+ * fixed order: results are bitwise reproducible.  workspace: larva_u8_metrics_workspace_bytes(h, w, mode) bytes,
+ * 8-byte aligned, the caller's; nothing is allocated or synchronised. */
+long long larva_u8_metrics_workspace_bytes(int h, int w, int mode);
+int larva_u8_metrics(const unsigned char* out, long long out_pitch, const unsigned char* truth, long long truth_pitch,
+                     int y0, int x0, int h, int w, int mode, int want_ssim, void* workspace,
+                     unsigned long long* result, void* stream);
+
 /* ---- fp16 inference (--precision fp16; csrc/conv3x3_f16.hip) -------------------------------------
  * Grad-free x4 forward at 48 channels on v_mfma_f32_16x16x32_f16: fp16 storage, fp32 accumulation.  fp16 tensors are
  * uint16_t bit images of IEEE half, CHANNELS-LAST [N][H][W][48] (not the fp32 NCHW of the entry points above); images

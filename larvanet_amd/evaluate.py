@@ -1,0 +1,151 @@
+"""Benchmark evaluator: counterpart of the reference's test.py.  Every truth image of --truth_path is paired with its
+low-resolution input of --input_path, upscaled, and scored on the device: PSNR and SSIM.
+
+    python -m larvanet_amd.evaluate --model=LarvaNet --num_modules=4 --num_blocks=4,4,4,4 --restore_path=model.pth \\
+        --input_path=LR --truth_path=HR [--output_path=SR] [--channel y|rgb] [--shave N] [--no_ssim] [--log FILE]
+        [--precision fp16] [--io_threads 8] [--depth 2]
+
+The two protocols super-resolution results are reported under:
+    --channel y (the default, with the default shave = scale)   Y-channel PSNR / SSIM with a border of `scale` pixels
+                                                                 shaved off: Set5, Set14, BSD100, Urban100, Manga109
+    --channel rgb --shave 0                                      RGB PSNR and multichannel SSIM on whole images: DIV2K
+Truth <stem>.png pairs with input <stem>.png or <stem>x<scale>.png (the DIV2K naming).  The images stay 8-bit and the
+metrics are computed where both images are (pipeline.evaluate_stream, csrc/larva_metrics.hip): per image a 64-byte
+record comes back, or the upscaled image too when --output_path asks for it.  Under torchrun file i goes to rank i mod
+world and the sums are all-reduced, as validate.py does."""
+import argparse
+import collections
+import concurrent.futures
+import importlib
+import os
+import time
+
+from . import dist as ldist
+from .upscale_images import _prefetched, io_threads, list_pngs, output_name, read_rgb, shard, write_rgb
+
+
+def build_parser():
+    p = argparse.ArgumentParser()
+    p.add_argument("--model", type=str, default="LarvaNet")
+    p.add_argument("--scale", type=int, default=4)
+    p.add_argument("--cuda_device", type=str, default=None)
+    p.add_argument("--restore_path", type=str, default=None,
+                   help="checkpoint (bare state_dict); omitted = freshly initialised weights")
+    p.add_argument("--restore_target", type=str)
+    p.add_argument("--restore_global_step", type=int, default=0)
+    p.add_argument("--input_path", type=str, default="LR")
+    p.add_argument("--truth_path", type=str, default="HR")
+    p.add_argument("--output_path", type=str, default=None, help="where to write the upscaled images; omitted = nowhere")
+    p.add_argument("--channel", type=str, default="y", choices=("y", "rgb"),
+                   help="y: BT.601 luma plane; rgb: the three colour planes (SSIM: their mean)")
+    p.add_argument("--shave", type=int, default=None, help="border pixels left out on every side; default: the scale")
+    p.add_argument("--no_ssim", action="store_true", help="PSNR only")
+    p.add_argument("--log", type=str, default=None, help="file that receives the printed result lines")
+    p.add_argument("--io_threads", type=int, default=None,
+                   help="PNG decode / encode threads; default and upper limit: this rank's share of the host's cores")
+    p.add_argument("--depth", type=int, default=2, help="images in flight on the device (1 = no copy overlap)")
+    return p
+
+
+def pair_files(truth_names, input_names, scale):
+    """[(truth name, input name)] for every truth name, in order: the input is the file with the truth's stem, or
+    <stem>x<scale>, and a .png extension of any letter case.  A truth without an input is a FileNotFoundError naming it."""
+    by_stem = {}
+    for name in input_names:
+        by_stem.setdefault(os.path.splitext(name)[0], name)
+    pairs = []
+    for name in truth_names:
+        stem = os.path.splitext(name)[0]
+        found = by_stem.get(stem) or by_stem.get("%sx%d" % (stem, scale))
+        if found is None:
+            raise FileNotFoundError("larvanet_amd.evaluate: no input image for truth %s (looked for %s.png and %sx%d.png)"
+                                    % (name, stem, stem, scale))
+        pairs.append((name, found))
+    return pairs
+
+
+def result_line(scale, index, count, result):
+    line = "x%d, %d/%d, psnr=%.4f" % (scale, index, count, result["psnr"])
+    return line if result["ssim"] is None else line + ", ssim=%.4f" % result["ssim"]
+
+
+def main(argv=None):
+    args, remaining = build_parser().parse_known_args(argv)
+    if args.cuda_device is not None and "LOCAL_RANK" not in os.environ:
+        os.environ["HIP_VISIBLE_DEVICES"] = args.cuda_device
+    if args.shave is not None and args.shave < 0:
+        raise ValueError("larvanet_amd.evaluate: --shave must be >= 0")
+    rank, world = ldist.init_from_env()
+    ldist.limit_host_threads()
+    pairs = pair_files(list_pngs(args.truth_path), list_pngs(args.input_path), args.scale)
+    print("data: %d images are prepared" % len(pairs))
+    mine = shard(pairs, rank, world)
+    if args.output_path is not None:
+        os.makedirs(args.output_path, exist_ok=True)
+    lines = []
+
+    def say(line):
+        print(line)
+        lines.append(line)
+
+    results = {}
+    sums = {"psnr": 0.0, "ssim": 0.0, "count": 0.0}
+    device = "cuda" if ldist.active() else "cpu"   # (a rank with an empty shard still takes part in the sums)
+    begin = time.perf_counter()
+    if mine:   # (an empty shard launches nothing and prepares no model)
+        from . import pipeline
+        print("prepare model - %s" % args.model)
+        model = importlib.import_module("larvanet_amd.models." + args.model).create_model()
+        _, remaining = model.parse_args(remaining)
+        model.prepare(is_training=False, scales=[args.scale], global_step=args.restore_global_step)
+        if remaining:
+            print("WARNING: found unhandled arguments: %s" % remaining)
+        if args.restore_path is not None:
+            model.restore(ckpt_path=args.restore_path, target=args.restore_target)
+            print("restored the model")
+        device = model.device
+        print("begin evaluation")
+        threads = io_threads(args.io_threads)
+        keep = args.output_path is not None
+        writes = collections.deque()
+
+        def read_pair(names):
+            return read_rgb(os.path.join(args.input_path, names[1])), read_rgb(os.path.join(args.truth_path, names[0]))
+
+        begin = time.perf_counter()
+        with concurrent.futures.ThreadPoolExecutor(max_workers=threads) as pool:
+            decoded = _prefetched(pool, read_pair, mine, ahead=threads + args.depth)
+            stream = pipeline.evaluate_stream(model, decoded, args.scale, shave=args.shave, channel=args.channel,
+                                              ssim=not args.no_ssim, depth=args.depth, keep_images=keep)
+            for i, item in enumerate(stream):
+                result, image = item if keep else (item, None)
+                if keep:
+                    writes.append(pool.submit(write_rgb, image, os.path.join(args.output_path, output_name(mine[i][0]))))
+                    while len(writes) > threads:   # (bounds the results waiting to be encoded)
+                        writes.popleft().result()
+                results[mine[i][0]] = result
+                sums["psnr"] += result["psnr"]
+                sums["ssim"] += result["ssim"] or 0.0
+                sums["count"] += 1
+                say(result_line(args.scale, i + 1, len(mine), result))
+            for w in writes:
+                w.result()
+    duration = time.perf_counter() - begin
+    total = {k: ldist.allreduce_scalar_sum(v, device) for k, v in sums.items()}
+    if total["count"]:
+        say("finished")
+        mean = "- average psnr=%.4f" % (total["psnr"] / total["count"])
+        if not args.no_ssim:
+            mean += ", ssim=%.4f" % (total["ssim"] / total["count"])
+        say(mean)
+        say("- duration: %.4fs" % duration)
+    else:
+        say("finished")
+    if args.log is not None and rank == 0:
+        with open(args.log, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return results
+
+
+if __name__ == "__main__":
+    main()

@@ -145,6 +145,10 @@ SIGNATURES = {
                                                ctypes.c_void_p]),
     "larva_f32_chw_to_u8_hwc": (ctypes.c_int, [_c_float_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_void_p]),
+    "larva_u8_metrics_workspace_bytes": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "larva_u8_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 _lib = None

@@ -1015,3 +1015,86 @@ def f32_chw_to_u8_hwc(x, out=None):
     _chk_u8(out, "out", (N, H, W, 3))
     hip_lib.check(lib.larva_f32_chw_to_u8_hwc(x.data_ptr(), out.data_ptr(), N, H, W, _stream()), "larva_f32_chw_to_u8_hwc")
     return out
+
+
+# ------------------------------------------------------------------ benchmark metrics (csrc/larva_metrics.hip)
+METRIC_CHANNELS = {"rgb": 0, "y": 1}
+METRIC_RESULT_WORDS = 8   # int64 words of a result record (include/larva_hip.h)
+SSIM_WINDOW = 11
+
+
+def _chk_u8_image(t, name):
+    """One uint8 image [H][W][3] (torch.uint8, contiguous, on the device)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("larvanet_amd: %s must be a uint8 tensor, got %s" % (name, type(t).__name__))
+    if t.dtype != torch.uint8:
+        raise TypeError("larvanet_amd: %s must be a uint8 tensor, got %s" % (name, t.dtype))
+    if t.dim() != 3 or int(t.shape[2]) != 3 or min(t.shape) < 1:
+        raise ValueError("larvanet_amd: %s must be [H][W][3], got %s" % (name, tuple(t.shape)))
+    if not t.is_cuda:
+        raise RuntimeError("larvanet_amd: %s must be a tensor on a HIP device (no CPU path exists)" % name)
+    if not t.is_contiguous():
+        raise RuntimeError("larvanet_amd: %s must be contiguous" % name)
+    return t.data_ptr()
+
+
+def metric_window(out_shape, truth_shape, shave, ssim):
+    """(y0, x0, h, w) of the evaluation window: the truth cropped top-left to the output, both shaved by `shave`.
+    Raises ValueError for what no launch may see: a truth smaller than the output, a negative shave, an empty window,
+    a window below 11 pixels when SSIM is wanted."""
+    oh, ow = int(out_shape[0]), int(out_shape[1])
+    th, tw = int(truth_shape[0]), int(truth_shape[1])
+    shave = int(shave)
+    if shave < 0:
+        raise ValueError("larvanet_amd: metrics need shave >= 0, got %d" % shave)
+    if th < oh or tw < ow:
+        raise ValueError("larvanet_amd: the truth image (%d x %d) is smaller than the output (%d x %d)" % (th, tw, oh, ow))
+    h, w = oh - 2 * shave, ow - 2 * shave
+    if h < 1 or w < 1:
+        raise ValueError("larvanet_amd: nothing is left of a %d x %d image after shaving %d pixels" % (oh, ow, shave))
+    if ssim and (h < SSIM_WINDOW or w < SSIM_WINDOW):
+        raise ValueError("larvanet_amd: SSIM needs a window of at least %d x %d pixels, got %d x %d"
+                         % (SSIM_WINDOW, SSIM_WINDOW, h, w))
+    return shave, shave, h, w
+
+
+def u8_metrics(out_u8_hwc, truth_u8_hwc, shave, channel, ssim=True, result=None):
+    """Squared error and SSIM of one uint8 [oh][ow][3] output against its uint8 [th][tw][3] truth (th >= oh, tw >= ow:
+    cropped top-left), both without `shave` border pixels, on the colour planes (channel "rgb") or the BT.601 luma plane
+    ("y").  Returns the device result record (int64 [8], include/larva_hip.h; `result` to write into a given one);
+    metrics_from_record turns its host copy into numbers.  Nothing comes back to the host here."""
+    lib = hip_lib.load()
+    if channel not in METRIC_CHANNELS:
+        raise ValueError("larvanet_amd: channel must be 'y' or 'rgb', got %r" % (channel,))
+    po = _chk_u8_image(out_u8_hwc, "out")
+    pt = _chk_u8_image(truth_u8_hwc, "truth")
+    if out_u8_hwc.device != truth_u8_hwc.device:
+        raise RuntimeError("larvanet_amd: out and truth are on different devices")
+    y0, x0, h, w = metric_window(out_u8_hwc.shape, truth_u8_hwc.shape, shave, ssim)
+    mode = METRIC_CHANNELS[channel]
+    nbytes = int(lib.larva_u8_metrics_workspace_bytes(h, w, mode))
+    if nbytes < 0:
+        raise ValueError("larvanet_amd: no metric kernel for a %d x %d window" % (h, w))
+    workspace = torch.empty(nbytes // 8, device=out_u8_hwc.device, dtype=torch.int64)
+    if result is None:
+        result = torch.empty(METRIC_RESULT_WORDS, device=out_u8_hwc.device, dtype=torch.int64)
+    elif (not isinstance(result, torch.Tensor) or result.dtype != torch.int64 or result.numel() != METRIC_RESULT_WORDS
+          or not result.is_contiguous() or result.device != out_u8_hwc.device):
+        raise RuntimeError("larvanet_amd: result must be a contiguous int64 [%d] tensor on the images' device"
+                           % METRIC_RESULT_WORDS)
+    hip_lib.check(lib.larva_u8_metrics(po, 3 * int(out_u8_hwc.shape[1]), pt, 3 * int(truth_u8_hwc.shape[1]), y0, x0, h, w,
+                                       mode, int(bool(ssim)), workspace.data_ptr(), result.data_ptr(), _stream()),
+                  "larva_u8_metrics")
+    return result
+
+
+def metrics_from_record(record):
+    """Host copy of a result record (int64 [8], CPU tensor or numpy) -> {"psnr", "ssim", "sse", "n"}; ssim is None when
+    the record was made without it."""
+    import numpy as np
+    from .metrics import psnr_from_sse
+    r = np.ascontiguousarray(record.numpy() if isinstance(record, torch.Tensor) else record, dtype=np.int64)
+    sse, count, n, planes = int(r.view(np.uint64)[0]), int(r[4]), int(r[5]), int(r[6])
+    sums = r.view(np.float64)[1:1 + planes]
+    ssim = None if count == 0 else float(sum(float(v) / count for v in sums) / planes)
+    return {"psnr": psnr_from_sse(sse, n), "ssim": ssim, "sse": sse, "n": n}

@@ -1038,13 +1038,14 @@ class LarvaNet(BaseModel):
                                  % (input_list[0].shape, a.shape))
         return np.ascontiguousarray(np.stack(input_list))
 
-    def _check_u8_tensor(self, x_u8):
+    def _check_u8_tensor(self, x_u8, who="upscale_u8_tensor", on_device=True):
         if not isinstance(x_u8, torch.Tensor) or x_u8.dtype != torch.uint8:
-            raise TypeError("larvanet_amd: upscale_u8_tensor takes a uint8 tensor, got %s"
-                            % (getattr(x_u8, "dtype", type(x_u8).__name__),))
+            raise TypeError("larvanet_amd: %s takes a uint8 tensor, got %s"
+                            % (who, getattr(x_u8, "dtype", type(x_u8).__name__),))
         if x_u8.dim() != 4 or x_u8.shape[3] != 3 or min(x_u8.shape) < 1:
-            raise ValueError("larvanet_amd: upscale_u8_tensor takes [N][H][W][3], got shape %s" % (tuple(x_u8.shape),))
-        _require_hip(x_u8)
+            raise ValueError("larvanet_amd: %s takes [N][H][W][3], got shape %s" % (who, tuple(x_u8.shape),))
+        if on_device:
+            _require_hip(x_u8)
         return x_u8.contiguous()
 
     def upscale_u8(self, input_list, scale):
@@ -1062,6 +1063,27 @@ class LarvaNet(BaseModel):
         x = self._check_u8_tensor(x_u8)
         with torch.no_grad():
             return self._infer_checked(x, u8=True).clone()
+
+    def evaluate_u8_tensor(self, x_u8, truth_u8, shave=None, channel="y", ssim=True):
+        """Upscale and score on the device: x_u8 uint8 [N][H][W][3] and truth_u8 uint8 [N][th][tw][3] (th >= sH, tw >= sW,
+        cropped top-left) on self.device -> one {"psnr", "ssim", "sse", "n"} per image (kernels.u8_metrics on what
+        upscale_u8_tensor returns).  shave=None shaves self.scale pixels; channel "y" (BT.601 luma) or "rgb"."""
+        x = self._check_u8_tensor(x_u8, "evaluate_u8_tensor", on_device=False)
+        truth = self._check_u8_tensor(truth_u8, "evaluate_u8_tensor", on_device=False)
+        if truth.shape[0] != x.shape[0]:
+            raise ValueError("larvanet_amd: evaluate_u8_tensor takes as many truth images as inputs, got %d and %d"
+                             % (truth.shape[0], x.shape[0]))
+        if channel not in K.METRIC_CHANNELS:
+            raise ValueError("larvanet_amd: channel must be 'y' or 'rgb', got %r" % (channel,))
+        shave = self.scale if shave is None else int(shave)
+        s = self.scale
+        K.metric_window((s * x.shape[1], s * x.shape[2]), truth.shape[1:3], shave, ssim)   # refusals before any launch
+        _require_hip(x)
+        _require_hip(truth)
+        with torch.no_grad():
+            out = self._infer_checked(x, u8=True)
+            records = torch.stack([K.u8_metrics(out[n], truth[n], shave, channel, ssim) for n in range(out.shape[0])])
+        return [K.metrics_from_record(r) for r in records.cpu().numpy()]
 
     def receptive_halo(self):
         """LR pixels beyond an output pixel's own LR pixel that can influence it: one per 3x3

@@ -12,6 +12,10 @@ largest image seen and viewed at each image's size.  The forward's result is cop
 8 MB image) into the slot's own output buffer on the compute stream, because a replayed graph's output buffer is
 overwritten by the next image of that shape and an eager result is the caching allocator's, which knows nothing of
 the copy stream.  A slot is reused only after its device-to-host copy has been waited for, which orders every reuse.
+
+evaluate_stream() is the same pipeline over (input, truth) pairs: the truth image travels in on the copy stream beside
+the input, the metric launch (kernels.u8_metrics) follows the forward on the compute stream, and only the 64-byte result
+record comes back unless the images are kept.
 """
 import collections
 
@@ -26,6 +30,7 @@ class _Slot:
         self.device = device
         self.copy_stream = copy_stream
         self.pin_in = self.pin_out = self.dev_in = self.dev_out = None
+        self.pin_truth = self.dev_truth = self.pin_record = self.dev_record = None   # evaluate_stream only
         self.pin_flag = torch.zeros(1, dtype=torch.int32, pin_memory=True)
         self.dev_flag = torch.zeros(1, dtype=torch.int32, device=device)
         self.dev_flag.record_stream(copy_stream)
@@ -51,6 +56,19 @@ class _Slot:
         self.dev_in = self._grown(self.dev_in, n, False)
         return self.pin_in[:n].view(shape), self.dev_in[:n].view(shape)
 
+    def views_truth(self, shape):
+        n = int(np.prod(shape))
+        self.pin_truth = self._grown(self.pin_truth, n, True)
+        self.dev_truth = self._grown(self.dev_truth, n, False)
+        return self.pin_truth[:n].view(shape), self.dev_truth[:n].view(shape)
+
+    def records(self, words):
+        if self.dev_record is None:
+            self.pin_record = torch.zeros(words, dtype=torch.int64, pin_memory=True)
+            self.dev_record = torch.zeros(words, dtype=torch.int64, device=self.device)
+            self.dev_record.record_stream(self.copy_stream)
+        return self.pin_record, self.dev_record
+
     def views_out(self, shape):
         n = int(np.prod(shape))
         self.pin_out = self._grown(self.pin_out, n, True)
@@ -58,12 +76,12 @@ class _Slot:
         return self.pin_out[:n].view(shape), self.dev_out[:n].view(shape)
 
 
-def _check_image(a):
+def _check_image(a, who="upscale_stream"):
     if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
-        raise TypeError("larvanet_amd: upscale_stream takes uint8 numpy arrays (decoded images), got %s"
-                        % (getattr(a, "dtype", type(a).__name__),))
+        raise TypeError("larvanet_amd: %s takes uint8 numpy arrays (decoded images), got %s"
+                        % (who, getattr(a, "dtype", type(a).__name__),))
     if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
-        raise ValueError("larvanet_amd: upscale_stream takes (H, W, 3) images, got shape %s" % (a.shape,))
+        raise ValueError("larvanet_amd: %s takes (H, W, 3) images, got shape %s" % (who, a.shape,))
 
 
 def upscale_stream(model, images, scale, depth=2):
@@ -82,7 +100,35 @@ def upscale_stream(model, images, scale, depth=2):
     return _stream(model, images, depth)
 
 
-def _stream(model, images, depth):
+def evaluate_stream(model, pairs, scale, shave=None, channel="y", ssim=True, depth=2, keep_images=False):
+    """Generator: (lr_uint8, truth_uint8) pairs of (H, W, 3) numpy images of any sizes -> per pair, in input order, the
+    dict kernels.metrics_from_record gives for model.upscale_u8([lr], scale)[0] against the truth ({"psnr", "ssim", "sse",
+    "n"}; see kernels.u8_metrics for shave / channel / ssim; shave=None shaves `scale` pixels), or with keep_images the
+    tuple (dict, upscaled uint8 image).  upscale_stream's pipeline: the truth goes in beside the input, the metrics run
+    behind the forward, the record (and the image only when kept) comes back.  A pair no metric is defined for (truth
+    smaller than the output, window below 11 pixels with SSIM) raises ValueError before anything of it is launched; fp16
+    overflow raises at the image's turn."""
+    from . import kernels as K
+    depth = int(depth)
+    if depth < 1:
+        raise ValueError("larvanet_amd: evaluate_stream needs depth >= 1")
+    if int(scale) != model.scale:
+        raise ValueError("larvanet_amd: this model upscales by %d, not by %r" % (model.scale, scale))
+    if channel not in K.METRIC_CHANNELS:
+        raise ValueError("larvanet_amd: channel must be 'y' or 'rgb', got %r" % (channel,))
+    shave = model.scale if shave is None else int(shave)
+    if shave < 0:
+        raise ValueError("larvanet_amd: metrics need shave >= 0, got %d" % shave)
+    if model.device.type != "cuda":
+        raise RuntimeError("larvanet_amd: evaluate_stream only runs on a HIP device (MI355X); there is no CPU fallback")
+    return _stream(model, pairs, depth, {"shave": shave, "channel": channel, "ssim": bool(ssim), "keep": bool(keep_images)})
+
+
+def _stream(model, images, depth, score=None):
+    """The pipeline of upscale_stream; with `score` (evaluate_stream's settings) the items are (input, truth) pairs."""
+    if score is not None:
+        from . import kernels as K
+    keep = score is None or score["keep"]
     compute = torch.cuda.current_stream()
     copy = torch.cuda.Stream()
     free = [_Slot(model.device, copy) for _ in range(depth)]
@@ -93,10 +139,13 @@ def _stream(model, images, depth):
     def issue_d2h(slot):
         if slot.d2h_issued:
             return
-        pin_out, dev_out = slot.views_out(slot.out_shape)
         with torch.cuda.stream(copy):
             copy.wait_event(slot.fwd)
-            pin_out.copy_(dev_out, non_blocking=True)
+            if keep:
+                pin_out, dev_out = slot.views_out(slot.out_shape)
+                pin_out.copy_(dev_out, non_blocking=True)
+            if score is not None:
+                slot.pin_record.copy_(slot.dev_record, non_blocking=True)
             if fp16:
                 slot.pin_flag.copy_(slot.dev_flag, non_blocking=True)
             slot.done.record(copy)
@@ -107,31 +156,50 @@ def _stream(model, images, depth):
         slot.done.synchronize()
         if fp16 and int(slot.pin_flag[0]):
             raise model.overflow_error()
-        out = np.array(slot.views_out(slot.out_shape)[0].numpy()[0])
+        out = np.array(slot.views_out(slot.out_shape)[0].numpy()[0]) if keep else None
+        result = None if score is None else K.metrics_from_record(slot.pin_record.numpy().copy())
         free.append(slot)
-        return out
+        if score is None:
+            return out
+        return (result, out) if keep else result
 
     try:
         with torch.no_grad():
             if fp16:
                 model_flag.zero_()
             for image in images:
-                _check_image(image)
+                if score is None:
+                    _check_image(image)
+                else:
+                    image, truth = image
+                    _check_image(image, "evaluate_stream")
+                    _check_image(truth, "evaluate_stream")
+                    K.metric_window((model.scale * image.shape[0], model.scale * image.shape[1]), truth.shape,
+                                    score["shave"], score["ssim"])
                 if len(inflight) == depth:
                     yield retire(inflight.popleft())
                 slot = free.pop()
                 shape = (1,) + tuple(image.shape)
                 pin_in, dev_in = slot.views_in(shape)
                 np.copyto(pin_in.numpy()[0], image)
+                if score is not None:
+                    pin_truth, dev_truth = slot.views_truth(tuple(truth.shape))
+                    np.copyto(pin_truth.numpy(), truth)
                 with torch.cuda.stream(copy):
                     dev_in.copy_(pin_in, non_blocking=True)
+                    if score is not None:
+                        dev_truth.copy_(pin_truth, non_blocking=True)
                     slot.h2d.record(copy)
                 if inflight:   # the previous image's way back, queued behind this image's way in
                     issue_d2h(inflight[-1])
                 compute.wait_event(slot.h2d)
                 out = model._infer_u8(dev_in)
                 slot.out_shape = tuple(out.shape)
-                slot.views_out(slot.out_shape)[1].copy_(out)
+                if keep:
+                    slot.views_out(slot.out_shape)[1].copy_(out)
+                if score is not None:   # (scored where the forward left it: nothing else runs on this stream in between)
+                    K.u8_metrics(out[0], dev_truth, score["shave"], score["channel"], score["ssim"],
+                                 result=slot.records(K.METRIC_RESULT_WORDS)[1])
                 if fp16:   # this image's overflow verdict; the model's flag starts the next image clean
                     slot.dev_flag.copy_(model_flag)
                     model_flag.zero_()
