@@ -389,6 +389,23 @@ int larva_f16_conv3x3_shuffle_base(const uint16_t* src, const uint16_t* wpk, con
 int larva_f16_conv3x3_shuffle_base_u8(const uint16_t* src, const uint16_t* wpk, const float* bias, const float* base,
                                       unsigned char* out, unsigned* flag, int N, int H, int W, void* stream);
 
+/* ---- geometric self-ensemble (--self_ensemble; csrc/larva_ensemble.hip) ------------------------------
+ * dihedral(a, t), t = 0..7, over the spatial axes: reverse rows if t & 1, then reverse columns if t & 2, then swap the axes
+ * if t & 4 (image_utils.dihedral).  larva_dihedral_inputs_u8 / _f32: in uint8 [N][H][W][3] / float [N][3][H][W] -> the
+ * eight images as batch slots of two fp32 NCHW tensors, exact: image n under t in slot 4 n + t of a [4N][3][H][W] for
+ * t < 4 and in slot 4 n + t - 4 of b [4N][3][W][H] for t >= 4.  One launch; each source pixel is read once.
+ *
+ * larva_dihedral_mean: a [4N][3][H][W] and b [4N][3][W][H] (the forward's outputs: H, W are the HR sizes here), v_t =
+ * dihedral_inv(slot t) -> E = (((((((v0 + v1) + v2) + v3) + v4) + v5) + v6) + v7) * 0.125f per pixel, fp32 adds in this
+ * order whatever the tile, into out_f32 [N][3][H][W] or, quantised as larva_f32_chw_to_u8_hwc does, into out_u8
+ * [N][H][W][3]; exactly one of the two is given, the other NULL.  One launch, no intermediate image; b is read through
+ * an LDS transpose.  Any N, H, W >= 1; 16-byte accesses where H and W are multiples of 4 and the pointers aligned, the
+ * values do not depend on the path. */
+int larva_dihedral_inputs_u8(const unsigned char* in, float* a, float* b, int N, int H, int W, void* stream);
+int larva_dihedral_inputs_f32(const float* in, float* a, float* b, int N, int H, int W, void* stream);
+int larva_dihedral_mean(const float* a, const float* b, float* out_f32, unsigned char* out_u8, int N, int H, int W,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@ issued in two or three large launches when backward ends (DeferredWgrad), all ex
 with batched launches (ExitsFn), and a tensor read by two convs gets its gradient from one stacked
 dgrad launch (JointBwd / JointInputGrad).
 """
+import contextlib
 import os
 
 import numpy as np
@@ -664,6 +665,19 @@ class HeadFn(torch.autograd.Function):
     # kernel's 4-pixel x 8-channel threads with 16-byte stores (profiles/r06_head_bicubic_ab.txt): "auto" = direct for
     # inference on more than LARGE_INFERENCE_PIXELS LR pixels (is_large_inference); 0 / 1 = never / always.
     direct = _head_direct_setting()
+    # The two head kernels agree to ~1e-5, not bit for bit.  A caller that runs images as extra batch slots and promises
+    # the bits of the plain call (the self-ensemble: 4 N or 8 N slots for N images) names the plain call's batch here,
+    # so that "auto" picks the kernel the plain call would (rule_batch_as).
+    rule_batch = None
+
+    @staticmethod
+    @contextlib.contextmanager
+    def rule_batch_as(n):
+        before, HeadFn.rule_batch = HeadFn.rule_batch, int(n)
+        try:
+            yield
+        finally:
+            HeadFn.rule_batch = before
 
     @staticmethod
     def forward(ctx, x, weight, bias, pc, x16=None, training=True):
@@ -673,7 +687,7 @@ class HeadFn(torch.autograd.Function):
         P = PaddedWidth.pitch_of(W) if _lw() is not None else W
         cout = int(weight.shape[0])
         training = bool(training) and bool(ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
-        want = HeadFn.direct if HeadFn.direct != "auto" else (not training and is_large_inference(N, H, W))
+        want = HeadFn.direct if HeadFn.direct != "auto" else (not training and is_large_inference(HeadFn.rule_batch or N, H, W))
         use_direct = want and C == 3 and cout % 16 == 0
         if x16 is not None:      # prepared by the step's prologue launch (step_prologue)
             pass

@@ -3,7 +3,10 @@ low-resolution input of --input_path, upscaled, and scored on the device: PSNR a
 
     python -m larvanet_amd.evaluate --model=LarvaNet --num_modules=4 --num_blocks=4,4,4,4 --restore_path=model.pth \\
         --input_path=LR --truth_path=HR [--output_path=SR] [--channel y|rgb] [--shave N] [--no_ssim] [--log FILE]
-        [--precision fp16] [--io_threads 8] [--depth 2]
+        [--precision fp16] [--self_ensemble] [--io_threads 8] [--depth 2]
+
+--self_ensemble (a model flag, like --precision) scores the geometric self-ensemble, the "+" column of SR tables: the
+mean of the eight flips / transposes of each image run through the network and mapped back, merged on the device.
 
 The two protocols super-resolution results are reported under:
     --channel y (the default, with the default shave = scale)   Y-channel PSNR / SSIM with a border of `scale` pixels

@@ -149,6 +149,12 @@ SIGNATURES = {
     "larva_u8_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "larva_dihedral_inputs_u8": (ctypes.c_int, [ctypes.c_void_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_int, ctypes.c_void_p]),
+    "larva_dihedral_inputs_f32": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_int, ctypes.c_void_p]),
+    "larva_dihedral_mean": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_void_p]),
 }
 
 _lib = None

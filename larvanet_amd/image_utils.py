@@ -1,8 +1,46 @@
 """Chop-forward of the reference (utils/image_utils.py:7-66): the LR image is cut into 2x2
 overlapping quadrants, each is upscaled on its own and the results are stitched at the quadrant
 boundaries.  This is approximate by design (overlap/2 = 10 LR px is less than the network's
-receptive-field radius of 35) and is reproduced as is."""
+receptive-field radius of 35) and is reproduced as is.
+
+Also the definitions of the geometric self-ensemble (--self_ensemble): the eight flips / transposes of the square."""
 import numpy as np
+
+
+def dihedral(a, t, axes=(0, 1)):
+    """Transform t (0..7) of the square on the two spatial axes `axes` = (rows, columns) of `a`: reverse the rows if
+    t & 1, then reverse the columns if t & 2, then swap the two axes if t & 4."""
+    r, c = axes
+    if t & 1:
+        a = np.flip(a, r)
+    if t & 2:
+        a = np.flip(a, c)
+    if t & 4:
+        a = np.swapaxes(a, r, c)
+    return a
+
+
+def dihedral_inv(a, t, axes=(0, 1)):
+    """The inverse of dihedral(., t): swap the axes if t & 4, then reverse the columns if t & 2, then the rows if t & 1."""
+    r, c = axes
+    if t & 4:
+        a = np.swapaxes(a, r, c)
+    if t & 2:
+        a = np.flip(a, c)
+    if t & 1:
+        a = np.flip(a, r)
+    return a
+
+
+def self_ensemble(f, x, axes=(0, 1)):
+    """E(x) = (((((((v0 + v1) + v2) + v3) + v4) + v5) + v6) + v7) * 0.125 in float32, v_t = dihedral_inv(f(dihedral(x, t)),
+    t): the host composition the device-side ensemble (--self_ensemble) equals bit for bit.  f maps an array to an
+    array with the same axes."""
+    acc = None
+    for t in range(8):
+        v = np.asarray(dihedral_inv(f(np.ascontiguousarray(dihedral(x, t, axes))), t, axes), dtype=np.float32)
+        acc = v if acc is None else acc + v
+    return acc * np.float32(0.125)
 
 
 def split_quadrants(image, overlap_size):

@@ -1017,6 +1017,61 @@ def f32_chw_to_u8_hwc(x, out=None):
     return out
 
 
+# ------------------------------------------------------------------ geometric self-ensemble (csrc/larva_ensemble.hip)
+def dihedral_inputs(x, out=None):
+    """The eight dihedral images (image_utils.dihedral) of x, uint8 [N][H][W][3] or float32 [N][3][H][W], as batch slots,
+    exact, in one launch -> (A float32 [4N][3][H][W], B float32 [4N][3][W][H]): image n under t is A[4 n + t] for t < 4
+    and B[4 n + t - 4] for t >= 4.  out = (A, B) to fill the caller's buffers."""
+    lib = hip_lib.load()
+    if isinstance(x, torch.Tensor) and x.dtype == torch.uint8:
+        _chk_u8(x, "x")
+        N, H, W = (int(v) for v in x.shape[:3])
+        fn, name = lib.larva_dihedral_inputs_u8, "larva_dihedral_inputs_u8"
+    else:
+        _chk(x, "x")
+        if x.dim() != 4 or int(x.shape[1]) != 3:
+            raise RuntimeError("larvanet_amd: x must be uint8 [N][H][W][3] or float32 [N][3][H][W], got %s" % (tuple(x.shape),))
+        N, _, H, W = (int(v) for v in x.shape)
+        fn, name = lib.larva_dihedral_inputs_f32, "larva_dihedral_inputs_f32"
+    if min(N, H, W) < 1:
+        raise RuntimeError("larvanet_amd: x must not be empty, got %s" % (tuple(x.shape),))
+    if out is None:
+        out = (torch.empty((4 * N, 3, H, W), device=x.device, dtype=torch.float32),
+               torch.empty((4 * N, 3, W, H), device=x.device, dtype=torch.float32))
+    a, b = out
+    _chk(a, "A", (4 * N, 3, H, W))
+    _chk(b, "B", (4 * N, 3, W, H))
+    hip_lib.check(fn(x.data_ptr(), a.data_ptr(), b.data_ptr(), N, H, W, _stream()), name)
+    return a, b
+
+
+def dihedral_mean(a, b, u8=False, out=None):
+    """The self-ensemble's merge in one launch: a float32 [4N][3][H][W] and b float32 [4N][3][W][H] (the forward's outputs
+    for dihedral_inputs' A and B) -> the fixed-order fp32 mean of the eight images mapped back (image_utils.dihedral_inv),
+    float32 [N][3][H][W], or with u8 its uint8 [N][H][W][3] form (f32_chw_to_u8_hwc of the former, bit for bit)."""
+    lib = hip_lib.load()
+    _chk(a, "A")
+    if a.dim() != 4 or int(a.shape[1]) != 3 or int(a.shape[0]) % 4 or min(a.shape) < 1:
+        raise RuntimeError("larvanet_amd: A must be [4N][3][H][W], got %s" % (tuple(a.shape),))
+    n4, _, H, W = (int(v) for v in a.shape)
+    _chk(b, "B", (n4, 3, W, H))
+    if b.device != a.device:
+        raise RuntimeError("larvanet_amd: A and B must be on one device")
+    N = n4 // 4
+    if u8:
+        if out is None:
+            out = torch.empty((N, H, W, 3), device=a.device, dtype=torch.uint8)
+        _chk_u8(out, "out", (N, H, W, 3))
+        f32, q8 = None, out.data_ptr()
+    else:
+        if out is None:
+            out = torch.empty((N, 3, H, W), device=a.device, dtype=torch.float32)
+        _chk(out, "out", (N, 3, H, W))
+        f32, q8 = out.data_ptr(), None
+    hip_lib.check(lib.larva_dihedral_mean(a.data_ptr(), b.data_ptr(), f32, q8, N, H, W, _stream()), "larva_dihedral_mean")
+    return out
+
+
 # ------------------------------------------------------------------ benchmark metrics (csrc/larva_metrics.hip)
 METRIC_CHANNELS = {"rgb": 0, "y": 1}
 METRIC_RESULT_WORDS = 8   # int64 words of a result record (include/larva_hip.h)

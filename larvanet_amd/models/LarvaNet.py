@@ -361,6 +361,10 @@ class LarvaNet(BaseModel):
                             help="Activation precision of inference (upscale / test / fwd_runtime): fp16 stores "
                                  "activations in fp16 and accumulates in fp32 (x4, --num_filters 48 only). "
                                  "Training is always fp32.")
+        parser.add_argument("--self_ensemble", action="store_true",
+                            help="Geometric self-ensemble (x8) in upscale / upscale_u8 / evaluate_u8_tensor and the "
+                                 "streams: the mean of the image's eight flips and transposes run through the network "
+                                 "and mapped back, merged on the device.")
 
     def parse_args(self, args):
         parser = argparse.ArgumentParser()
@@ -905,30 +909,50 @@ class LarvaNet(BaseModel):
             return self._forward_nograd(x_u8, True)
         return self._capture_or_run(x_u8, True)
 
-    def _capture_or_run(self, x, u8):
-        """The grad-free forward of a small device batch `x` (uint8 images when u8): a shape seen once runs eagerly; seen
-        for the second time it is captured (at most four graphs per table; False marks a capture that failed) and
-        replayed from then on."""
-        cache = self.__dict__.setdefault("_infer_graphs_u8" if u8 else "_infer_graphs", {})
-        seen = self.__dict__.setdefault("_infer_seen_u8" if u8 else "_infer_seen", {})
+    def _infer_ensemble(self, x, u8=False):
+        """The x8 self-ensemble of a device batch (uint8 [N][H][W][3] when u8, else float [N][3][H][W]) with _infer's
+        rules: the large-inference rule asks about each forward's batch (8 N slots of a square image, 4 N otherwise);
+        graphs are kept under (shape, precision, "u8" / "f32", "se") in a table of their own (_infer_graphs_se, its own
+        limit of four), so the plain float and uint8 paths capture exactly what they would without this one.  A captured
+        ensemble holds the input launch, the forward(s) and the merge launch."""
+        n = int(x.shape[0])
+        h, w = (int(v) for v in (x.shape[1:3] if u8 else x.shape[2:4]))
+        if not (self.use_hip_graph and x.is_cuda) or is_large_inference((8 if h == w else 4) * n, h, w):
+            return self._forward_nograd(x, u8, True)
+        return self._capture_or_run(x, u8, True)
+
+    def _infer_u8_images(self, x_u8):
+        """What upscale_u8 / evaluate_u8_tensor and the streams (pipeline.py) run on a uint8 device batch: _infer_u8, or
+        under --self_ensemble the ensemble."""
+        return self._infer_ensemble(x_u8, True) if self._self_ensemble() else self._infer_u8(x_u8)
+
+    def _capture_or_run(self, x, u8, ensemble=False):
+        """The grad-free forward of a small device batch `x` (uint8 images when u8; the self-ensemble when ensemble): a
+        shape seen once runs eagerly; seen for the second time it is captured (at most four graphs per table; False
+        marks a capture that failed) and replayed from then on."""
+        table = "_se" if ensemble else ("_u8" if u8 else "")
+        cache = self.__dict__.setdefault("_infer_graphs" + table, {})
+        seen = self.__dict__.setdefault("_infer_seen" + table, {})
         key = (tuple(x.shape), self._precision()) + (("u8",) if u8 else ())
+        if ensemble:
+            key = (tuple(x.shape), self._precision(), "u8" if u8 else "f32", "se")
         ent = cache.get(key)
         if ent is None:
             if len(seen) > 512:   # (a long run over images of ever new sizes: forget the counts)
                 seen.clear()
             seen[key] = seen.get(key, 0) + 1
             if seen[key] < 2 or len(cache) >= 4:
-                return self._forward_nograd(x, u8)
-            ent = cache[key] = self._capture_infer(x, u8)
+                return self._forward_nograd(x, u8, ensemble)
+            ent = cache[key] = self._capture_infer(x, u8, ensemble)
         if ent is False:
-            return self._forward_nograd(x, u8)
+            return self._forward_nograd(x, u8, ensemble)
         self._refresh_inference_weights()   # weights restored / stepped since the capture: repack (outside the graph)
         static_x, graph, out = ent
         static_x.copy_(x)
         graph.replay()
         return out
 
-    def _capture_infer(self, x, u8=False):
+    def _capture_infer(self, x, u8=False, ensemble=False):
         static_x = x.clone()
         try:
             side = torch.cuda.Stream()
@@ -936,12 +960,12 @@ class LarvaNet(BaseModel):
             with torch.cuda.stream(side):
                 for _ in range(2):
                     with self._infer_scope():
-                        self._forward_nograd(static_x, u8)
+                        self._forward_nograd(static_x, u8, ensemble)
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
                 with self._infer_scope():
-                    out = self._forward_nograd(static_x, u8)
+                    out = self._forward_nograd(static_x, u8, ensemble)
             return static_x, graph, out
         except Exception as e:   # an optimisation only
             if self.strict_graph:
@@ -958,10 +982,38 @@ class LarvaNet(BaseModel):
         """The fp16 forward when the model runs at --precision fp16, else None: the one place precision is decided."""
         return self.model.half_forward() if self._precision() == "fp16" else None
 
-    def _forward_nograd(self, x, u8=False):
+    def _self_ensemble(self):
+        """Does this model run the x8 self-ensemble in its image entry points (--self_ensemble)?  The one place it is
+        decided; grad-enabled calls, test, fwd_runtime and the validation of training never ask."""
+        return bool(getattr(getattr(self, "args", None), "self_ensemble", False))
+
+    def _forward_ensemble(self, x, u8):
+        """E(x) of image_utils.self_ensemble on the device (no graph): one launch builds the eight inputs as batch slots,
+        the existing fp32 / fp16 forward runs them (one forward of 8 N for a square image, else one of 4 N per shape) and
+        ends in fp32 HR images, one launch maps them back, averages and (u8) quantises.  A pixel's result does not depend
+        on its batch slot, so this is the composition of eight plain calls bit for bit; the head kernel, whose two forms
+        do differ, is chosen as the plain call of these N images would choose it."""
+        n = int(x.shape[0])
+        h, w = (int(v) for v in (x.shape[1:3] if u8 else x.shape[2:4]))
+        half = self._half()
+        run = half if half is not None else self.model
+        with HeadFn.rule_batch_as(n):
+            if h == w:
+                both = torch.empty((8 * n, 3, h, w), device=x.device, dtype=torch.float32)
+                K.dihedral_inputs(x, out=(both[:4 * n], both[4 * n:]))
+                out = run(both).contiguous()
+                a, b = out[:4 * n], out[4 * n:]
+            else:
+                a, b = K.dihedral_inputs(x)
+                a, b = run(a).contiguous(), run(b).contiguous()
+        return K.dihedral_mean(a, b, u8=u8)
+
+    def _forward_nograd(self, x, u8=False, ensemble=False):
         """The inference forward at the model's precision (no graph).  u8: uint8 [N][H][W][3] -> uint8 [N][sH][sW][3],
         the float forward over the exactly converted image, then round half to even + clamp on the device (at fp16 the
-        leg end's epilogue stores the bytes itself)."""
+        leg end's epilogue stores the bytes itself).  ensemble: the x8 self-ensemble of either form."""
+        if ensemble:
+            return self._forward_ensemble(x.contiguous(), u8)
         half = self._half()
         if u8:
             x = K.u8_hwc_to_f32_chw(x)
@@ -995,13 +1047,16 @@ class LarvaNet(BaseModel):
         half = self._half()
         return half is not None and half.take_overflow()
 
-    def _infer_checked(self, x, u8=False):
+    def _infer_checked(self, x, u8=False, ensemble=False):
         """upscale / upscale_tensor / test and their uint8 forms: an fp16 activation that left the fp16 range is an
-        error, not a result."""
+        error, not a result.  ensemble: the caller is an image entry point of a model with --self_ensemble."""
         half = self._half()
         if half is not None:
             half.clear_overflow()
-        out = self._infer_u8(x) if u8 else self._infer(x)
+        if ensemble:
+            out = self._infer_ensemble(x, u8)
+        else:
+            out = self._infer_u8(x) if u8 else self._infer(x)
         if self.fp16_overflowed():
             raise self.overflow_error()
         return out
@@ -1013,12 +1068,12 @@ class LarvaNet(BaseModel):
     def upscale(self, input_list, scale):
         """list of CHW numpy images -> (N, 3, 4H, 4W) float32 numpy (models/LarvaNet.py:163-171)."""
         with torch.no_grad():
-            return self._infer_checked(self._to_input_tensor(input_list)).detach().cpu().numpy()
+            return self._infer_checked(self._to_input_tensor(input_list), ensemble=self._self_ensemble()).detach().cpu().numpy()
 
     def upscale_tensor(self, input_list):
         """upscale() without the trip to the host: (N, 3, 4H, 4W) float32 on self.device."""
         with torch.no_grad():
-            return self._infer_checked(self._to_input_tensor(input_list)).detach().clone()
+            return self._infer_checked(self._to_input_tensor(input_list), ensemble=self._self_ensemble()).detach().clone()
 
     # ------------------------------------------------------------------ 8-bit images in, 8-bit images out
     def _check_u8_images(self, input_list, scale):
@@ -1056,13 +1111,13 @@ class LarvaNet(BaseModel):
         with torch.no_grad():
             x = torch.from_numpy(batch).to(self.device)
             _require_hip(x)
-            return self._infer_checked(x, u8=True).cpu().numpy()
+            return self._infer_checked(x, u8=True, ensemble=self._self_ensemble()).cpu().numpy()
 
     def upscale_u8_tensor(self, x_u8):
         """upscale_u8 without the trips to and from the host: uint8 [N][H][W][3] on self.device -> uint8 [N][sH][sW][3]."""
         x = self._check_u8_tensor(x_u8)
         with torch.no_grad():
-            return self._infer_checked(x, u8=True).clone()
+            return self._infer_checked(x, u8=True, ensemble=self._self_ensemble()).clone()
 
     def evaluate_u8_tensor(self, x_u8, truth_u8, shave=None, channel="y", ssim=True):
         """Upscale and score on the device: x_u8 uint8 [N][H][W][3] and truth_u8 uint8 [N][th][tw][3] (th >= sH, tw >= sW,
@@ -1081,7 +1136,7 @@ class LarvaNet(BaseModel):
         _require_hip(x)
         _require_hip(truth)
         with torch.no_grad():
-            out = self._infer_checked(x, u8=True)
+            out = self._infer_checked(x, u8=True, ensemble=self._self_ensemble())
             records = torch.stack([K.u8_metrics(out[n], truth[n], shave, channel, ssim) for n in range(out.shape[0])])
         return [K.metrics_from_record(r) for r in records.cpu().numpy()]
 

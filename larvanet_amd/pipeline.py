@@ -1,7 +1,8 @@
 """Images in, images out, with the host link hidden behind the forward.
 
-upscale_stream() walks an iterable of uint8 (H, W, 3) images of any mix of sizes through model._infer_u8 and yields the
-uint8 (sH, sW, 3) results in input order.  Image i+1's host-to-device copy and image i-1's device-to-host copy run on
+upscale_stream() walks an iterable of uint8 (H, W, 3) images of any mix of sizes through model._infer_u8 (under
+--self_ensemble: the device-side x8 ensemble, model._infer_u8_images decides) and yields the uint8 (sH, sW, 3) results in
+input order.  Image i+1's host-to-device copy and image i-1's device-to-host copy run on
 ONE extra stream beside image i's forward:
 
     copy stream     H2D(0) H2D(1) D2H(0) H2D(2) D2H(1) ...        (issue order; D2H(i) waits for forward i's event)
@@ -193,7 +194,7 @@ def _stream(model, images, depth, score=None):
                 if inflight:   # the previous image's way back, queued behind this image's way in
                     issue_d2h(inflight[-1])
                 compute.wait_event(slot.h2d)
-                out = model._infer_u8(dev_in)
+                out = model._infer_u8_images(dev_in)   # (the x8 self-ensemble under --self_ensemble)
                 slot.out_shape = tuple(out.shape)
                 if keep:
                     slot.views_out(slot.out_shape)[1].copy_(out)

@@ -2,7 +2,11 @@
 is written as <output_path>/<stem>.png.
 
     python -m larvanet_amd.upscale_images --model=LarvaNet --num_modules=4 --num_blocks=4,4,4,4 \\
-        --restore_path=model.pth --input_path=LR --output_path=SR [--precision fp16] [--io_threads 8]
+        --restore_path=model.pth --input_path=LR --output_path=SR [--precision fp16] [--self_ensemble]
+        [--io_threads 8]
+
+--self_ensemble (a model flag, like --precision) writes the geometric self-ensemble: the mean of the eight flips /
+transposes of each image run through the network and mapped back, merged on the device.
 
 The images stay 8-bit end to end (pipeline.upscale_stream over model._infer_u8): PNGs are decoded and encoded by a
 thread pool around the stream, a quarter of the float path's bytes cross the host link, and the copies of neighbouring
