@@ -512,6 +512,11 @@ class DeferredWgrad:
         return [t for _, _, chunk in launches[:n_early] for j in chunk for t in (j["dw"], j["db"]) if t is not None]
 
     @classmethod
+    def has_late(cls):
+        """Did a split flush hold launches back for flush_late()?"""
+        return bool(cls._late)
+
+    @classmethod
     def late_targets(cls):
         return [t for _, _, chunk in cls._late for j in chunk for t in (j["dw"], j["db"]) if t is not None]
 

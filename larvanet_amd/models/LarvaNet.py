@@ -20,9 +20,11 @@ import torch.nn as nn
 
 from .. import dist as ldist
 from .. import kernels as K
-from ..autograd import (BodyFn, DualChain, ExitFn, ExitsFn, GradBucket, HeadFn, L1LossFn, LegFn, LossTerm, PackedConv, PaddedWidth, mean_of_terms,
+from ..autograd import (BodyFn, DeferredWgrad, DualChain, ExitFn, ExitsFn, GradBucket, HeadFn, L1LossFn, LegFn, LossTerm, PackedConv, PaddedWidth, mean_of_terms,
                         StepScope, is_large_inference, pack_all)
 from ..autograd import step_prologue as autograd_step_prologue
+from ..captured_step import CapturedStep, LossCopy
+from ..infer_graphs import Form, GraphTable
 from ..optim import FlatAdamW, flatten_parameters
 from ..metrics import image_psnr, image_to_uint8, fit_truth_image_size
 from .base import BaseModel
@@ -307,11 +309,8 @@ class LarvaNet(BaseModel):
         super().__init__()
         self.volume_per_step = 0
         self.sync_loss = True
-        # sync_loss with a captured step: `return loss.item()` (models/LarvaNet.py:139) waits for the forward only.
-        # "poll": one graph; the launch that finishes the loss right after the exits also stores it into a float
-        # (+ a sequence number) of coherent pinned host memory (kernels.HostCell), which the host polls.  "split": forward | backward
-        # as two graphs, the loss is copied out between them on a side stream and the host waits for that event.
-        # False: the host waits for the whole step.
+        # sync_loss with a captured step: `return loss.item()` (models/LarvaNet.py:139) waits for the forward only, in one
+        # of the two ways of captured_step.CapturedStep ("poll" or "split").  False: the host waits for the whole step.
         self.early_loss = {"0": False, "split": "split"}.get(os.environ.get("LARVA_EARLY_LOSS", "poll"), "poll")
         self.use_hip_graph = os.environ.get("LARVA_HIP_GRAPH", "1") != "0"
         self.hip_graph_fell_back = None   # reason, if a capture failed and the step went eager
@@ -333,6 +332,20 @@ class LarvaNet(BaseModel):
         # measurement: run the data-parallel step's weight-gradient schedule (two launch groups, so that the first
         # group's slice of the bucket can be all-reduced beside the second) on ONE GPU, without collectives
         self.force_split_backward = os.environ.get("LARVA_FORCE_SPLIT", "0") != "0"
+        self.args = None
+        self.precision = "fp32"       # (prepare() takes it from --precision)
+        self.grad_bucket = None
+        self.time_allreduce = False   # bench.py: time every exposed all-reduce, as a pair of events in ...
+        self.allreduce_events = []
+        # prepare() forgets what was captured for the module it replaces: the training step (a CapturedStep or None) ...
+        self._step = None
+        self._infer_graphs, self._infer_graphs_u8, self._infer_graphs_se = GraphTable(), GraphTable(), GraphTable()
+        # ... and the step in flight: d loss / d loss, the second half of a split backward, the bucket's split (_step_body)
+        self._one = self._late = self._early_lo = None
+        self._loss_in_flight = False  # how this step's loss reaches the host early: False, "poll" or "split"
+        # the early-loss hand-offs by mode, made at first use and kept across captures (a kernels.HostCell's sequence count
+        # runs on): {"poll": HostCell, "split": captured_step.LossCopy}
+        self._handoffs = {}
 
     # ------------------------------------------------------------------ flags
     has_cooldown = True   # this flag set has --cooldown (V2's, which LarvaLeg / LarvaLegV2 share, does not)
@@ -408,6 +421,11 @@ class LarvaNet(BaseModel):
 
         self.device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() \
             else torch.device("cpu")
+        # whatever was captured reads the module, the gradient bucket and the optimizer that are replaced below
+        self._step = self._one = self._late = self._early_lo = self.grad_bucket = None
+        self._loss_in_flight = False
+        for table in (self._infer_graphs, self._infer_graphs_u8, self._infer_graphs_se):
+            table.clear()
         margs = copy.copy(self.args)
         margs.scale = self.scale
         self.model = self.module_class(args=margs).to(self.device)
@@ -425,7 +443,6 @@ class LarvaNet(BaseModel):
                 self.optim = FlatAdamW(params, flat, self.grad_bucket, lr=self.args.lr)
                 self._choose_dp_schedule()
             else:
-                self.grad_bucket = None
                 self.optim = torch.optim.AdamW(params, lr=self.args.lr)
                 if self.overlap_allreduce == "auto":   # (no flat bucket on the CPU: nothing to overlap)
                     self.overlap_allreduce = False
@@ -468,10 +485,9 @@ class LarvaNet(BaseModel):
     # ------------------------------------------------------------------ training
     def _grad_one(self, loss):
         """d loss / d loss = 1 as a persistent tensor (autograd would fill a new one every step)."""
-        one = getattr(self, "_one", None)
-        if one is None or one.device != loss.device:
-            one = self._one = torch.ones((), device=loss.device, dtype=loss.dtype)
-        return one
+        if self._one is None or self._one.device != loss.device:
+            self._one = torch.ones((), device=loss.device, dtype=loss.dtype)
+        return self._one
 
     def _num_loss_terms(self):
         return self.args.num_modules
@@ -533,15 +549,11 @@ class LarvaNet(BaseModel):
             terms.append(term)
         return mean_of_terms(terms), out
 
-    # hipGraph path: one step issues ~330 short kernels; launched one by one from Python the GPU
-    # idles between them, so forward + backward are captured once per batch shape and replayed.
+    # hipGraph path (captured_step.py): forward + backward are captured once per batch shape and replayed
     def _graph_key(self, input_tensor, truth_tensor):
-        return (tuple(input_tensor.shape), tuple(truth_tensor.shape), str(input_tensor.device), self._early_loss_capture())
-
-    def _early_loss_capture(self):
-        if not (self.sync_loss and self.early_loss):
-            return False
-        return "split" if self.early_loss == "split" else "poll"
+        """What a CapturedStep is good for: the shapes, the device and, last, the early-loss mode of the capture."""
+        mode = ("split" if self.early_loss == "split" else "poll") if self.sync_loss and self.early_loss else False
+        return (tuple(input_tensor.shape), tuple(truth_tensor.shape), str(input_tensor.device), mode)
 
     def _scope(self, early_loss=False):
         # seed_grad: _forward_backward seeds loss.backward() with _grad_one and nothing scales the loss
@@ -550,7 +562,7 @@ class LarvaNet(BaseModel):
         # consumer per body output (joint input gradients) with every weight gradient deferred
         lazy_fwd = self._exits_batched()
         lazy_bwd = (lazy_fwd and self.joint_input_grads and self.defer_wgrad and self._single_consumer_features()
-                    and getattr(self, "grad_bucket", None) is not None and self.grad_bucket.intact(self.model))
+                    and self.grad_bucket is not None and self.grad_bucket.intact(self.model))
         return StepScope(defer_wgrad=self.defer_wgrad, split_flush=self._split_backward(),
                          joint_input_grads=self.joint_input_grads, seed_grad=1.0, dual_chain=self.dual_chain,
                          lazy_chain_joins=(lazy_fwd, lazy_bwd), early_loss=early_loss)
@@ -562,109 +574,41 @@ class LarvaNet(BaseModel):
     def _split_backward(self):
         """Data parallel with in-place gradients: backward ends in two halves so that the
         all-reduce of the first overlaps the weight-gradient kernels of the second."""
-        bucket = getattr(self, "grad_bucket", None)
         return (self.overlap_allreduce is True and self.defer_wgrad and (ldist.active() or self.force_split_backward)
-                and bucket is not None and bucket.intact(self.model))
+                and self.grad_bucket is not None and self.grad_bucket.intact(self.model))
 
-    def _note_early(self, scope):
-        """Where the gradients that are complete after the first half live in the flat bucket:
-        self._early_lo = first float of that suffix, or None = no overlap (one collective)."""
-        self._early_lo = None
-        from ..autograd import DeferredWgrad
-        bucket = getattr(self, "grad_bucket", None)
-        if not scope.split_flush or bucket is None or not scope.early_targets:
-            return
-        early, late = bucket.span(scope.early_targets), bucket.span(DeferredWgrad.late_targets())
-        if early is None or late is None:
-            return
-        if early[1] == bucket.flat.numel() and late[1] <= early[0]:
-            self._early_lo = early[0]
+    def _step_body(self, input_tensor, truth_tensor, early_loss=False, cut=None):
+        """Forward and backward of one batch in one StepScope, eagerly or under capture -> (loss, last output, early_lo).
+        cut: called between the two (the "split" capture changes graphs there).  early_lo: where the gradients complete
+        after the first half of a split flush live in the flat bucket (the first float of that suffix), or None = no overlap."""
+        with self._scope(early_loss=early_loss) as scope:
+            loss, out = self._exit_losses(input_tensor, truth_tensor)
+            if cut is not None:
+                cut()
+            loss.backward(self._grad_one(loss))
+        bucket, early_lo = self.grad_bucket, None
+        if scope.split_flush and bucket is not None and scope.early_targets:
+            early, late = bucket.span(scope.early_targets), bucket.span(DeferredWgrad.late_targets())
+            if early is not None and late is not None and early[1] == bucket.flat.numel() and late[1] <= early[0]:
+                early_lo = early[0]
+        return loss, out, early_lo
 
-    def _capture_step(self, input_tensor, truth_tensor):
-        from ..autograd import DeferredWgrad
-        self._static_in = input_tensor.clone()
-        self._static_truth = truth_tensor.clone()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):  # warm-up outside capture (lazy kernel attributes, allocator pools)
-                self._zero_grad()
-                with self._scope():
-                    loss, _ = self._exit_losses(self._static_in, self._static_truth)
-                    loss.backward(self._grad_one(loss))
-                DeferredWgrad.flush_late()
-        torch.cuda.current_stream().wait_stream(side)
-        self._zero_grad()
-        graph = torch.cuda.CUDAGraph()
-        self._graph_back = None
-        # thread_local: a process-group watchdog thread must not abort the capture
-        mode = self._early_loss_capture()
-        if mode == "split" and getattr(self, "_loss_host", None) is None:
-            self._loss_host = torch.empty((), dtype=torch.float32).pin_memory()
-            self._loss_stream = torch.cuda.Stream()
-            self._loss_done = torch.cuda.Event()
-            self._fwd_done = torch.cuda.Event()
-        if mode == "poll" and getattr(self, "_loss_cell", None) is None:
-            self._loss_cell = K.HostCell()
-        if mode != "split":
-            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                with self._scope(early_loss=self._loss_cell if mode else False) as scope:
-                    loss, out = self._exit_losses(self._static_in, self._static_truth)
-                    loss.backward(self._grad_one(loss))
-        else:
-            # forward | backward as two graphs over one memory pool: the loss is complete when the first one ends
-            scope = self._scope(early_loss=True)
-            back = torch.cuda.CUDAGraph()
-            scope.__enter__()
-            left = False
-            try:
-                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                    loss, out = self._exit_losses(self._static_in, self._static_truth)
-                    DualChain.join()
-                with torch.cuda.graph(back, pool=graph.pool(), capture_error_mode="thread_local"):
-                    loss.backward(self._grad_one(loss))
-                    left = True
-                    scope.__exit__(None, None, None)   # joins the chains, issues the queued weight gradients
-            finally:
-                if not left:
-                    scope.__exit__(RuntimeError, None, None)
-            self._graph_back = back
-        self._graph_polls = mode == "poll"
-        self._note_early(scope)
-        self._graph_late = None
-        if DeferredWgrad._late:  # second half of a split backward: its own graph, same memory pool
-            late = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(late, pool=graph.pool(), capture_error_mode="thread_local"):
-                DeferredWgrad.flush_late()
-            self._graph_late = late
-        self._graph, self._graph_loss, self._graph_out = graph, loss, out
-        self._graph_shape = self._graph_key(input_tensor, truth_tensor)
+    _graph_late = property(lambda self: self._step and self._step.late)   # (bench.py reports whether there is one)
 
     def input_buffers(self, input_shape, truth_shape):
         """The (input, truth) tensors the captured training step reads, or None while no step of
         that shape has been captured.  A producer on the device (dataloaders/device_patch_loader)
         writes the next batch straight into them and passes them to train_step_larva, which then
         skips its two copies into the graph's inputs."""
-        if not self.use_hip_graph or getattr(self, "_graph_shape", None) is None:
+        if not self.use_hip_graph or self._step is None:
             return None
-        if tuple(self._static_in.shape) != tuple(input_shape) or tuple(self._static_truth.shape) != tuple(truth_shape):
-            return None
-        return self._static_in, self._static_truth
-
-    def _stage_inputs(self, input_tensor, truth_tensor):
-        """The batch into the captured step's input buffers (train_larva.py:123-128 hands over fresh device tensors every
-        step), on the current stream, i.e. ordered behind whatever produced them.  (Round 4 also copied them on a stream
-        of its own beside the previous step's backward: 1.669-1.672 against 1.657-1.660 ms -- two cross-stream waits cost
-        more than the two 5 us copies they hide -- and, without an edge from the producer's stream, a race; removed.)"""
-        for dst, src in ((self._static_in, input_tensor), (self._static_truth, truth_tensor)):
-            if src.data_ptr() != dst.data_ptr():
-                dst.copy_(src)
+        return self._step.buffers(input_shape, truth_shape)
 
     def _zero_grad(self):
         """optim.zero_grad() of the reference (models/LarvaNet.py:112).  With the flat gradient
         bucket every backward overwrites the gradients in place, so nothing has to be cleared
         (and set_to_none would detach the bucket views)."""
-        bucket = getattr(self, "grad_bucket", None)
+        bucket = self.grad_bucket
         if bucket is not None and bucket.intact(self.model):
             return
         if bucket is not None:  # somebody replaced a .grad: stop writing in place
@@ -676,9 +620,14 @@ class LarvaNet(BaseModel):
     def _forward_backward(self, input_tensor, truth_tensor):
         """loss and gradients of one batch (models/LarvaNet.py:101-113)."""
         if self.use_hip_graph and input_tensor.is_cuda:
-            if getattr(self, "_graph_shape", None) != self._graph_key(input_tensor, truth_tensor):
+            key = self._graph_key(input_tensor, truth_tensor)
+            if self._step is None or self._step.key != key:
                 try:
-                    self._capture_step(input_tensor, truth_tensor)
+                    mode = key[-1]
+                    if mode and mode not in self._handoffs:
+                        self._handoffs[mode] = K.HostCell() if mode == "poll" else LossCopy()
+                    # (a capture that raises leaves _step as it was)
+                    self._step = CapturedStep(self, key, mode, self._handoffs.get(mode), input_tensor, truth_tensor)
                 except Exception as e:  # capture is an optimisation: fall back to plain launches
                     if self.strict_graph:
                         raise
@@ -689,30 +638,14 @@ class LarvaNet(BaseModel):
                     torch.cuda.synchronize()
                     DualChain.reset()   # (a capture that died mid-chain must not leave the chains marked as forked)
                     return self._forward_backward(input_tensor, truth_tensor)
-            # (a producer that filled input_buffers() in place hands the very same storage back)
-            self._stage_inputs(input_tensor, truth_tensor)
-            if self._graph_polls:
-                self._loss_cell.expect()   # this replay's store carries the next sequence number
-                self._loss_in_flight = "poll"
-            self._graph.replay()  # gradients are overwritten in place: no zero_grad needed
-            if self._graph_back is not None:
-                # the loss goes to pinned host memory on a stream of its own while backward runs
-                self._fwd_done.record()
-                with torch.cuda.stream(self._loss_stream):
-                    self._loss_stream.wait_event(self._fwd_done)
-                    self._loss_host.copy_(self._graph_loss, non_blocking=True)
-                    self._loss_done.record()
-                self._loss_in_flight = "event"
-                self._graph_back.replay()
-            self._late = self._graph_late.replay if self._graph_late is not None else None
-            return self._graph_loss, self._graph_out
-        from ..autograd import DeferredWgrad
+            step = self._step
+            step.stage(input_tensor, truth_tensor)
+            self._loss_in_flight, self._early_lo = step.mode, step.early_lo
+            loss, out, self._late = step.replay()
+            return loss, out
         self._zero_grad()
-        with self._scope() as scope:
-            loss, out = self._exit_losses(input_tensor, truth_tensor)
-            loss.backward(self._grad_one(loss))
-        self._note_early(scope)
-        self._late = DeferredWgrad.flush_late if DeferredWgrad._late else None
+        loss, out, self._early_lo = self._step_body(input_tensor, truth_tensor)
+        self._late = DeferredWgrad.flush_late if DeferredWgrad.has_late() else None
         return loss, out
 
     def _finish_backward(self):
@@ -720,9 +653,9 @@ class LarvaNet(BaseModel):
         (one flat bucket; the all-reduce of the half that is already complete runs on
         RCCL's stream beside the remaining weight-gradient kernels).  The 1/world_size of the
         mean is applied inside the optimizer kernel (FlatAdamW.mean_scale)."""
-        late, self._late = getattr(self, "_late", None), None
+        late, self._late = self._late, None
         ws = ldist.world_size()
-        bucket = getattr(self, "grad_bucket", None)
+        bucket = self.grad_bucket
         if not ldist.active() or bucket is None or not bucket.intact(self.model):
             if late is not None:
                 late()
@@ -730,8 +663,8 @@ class LarvaNet(BaseModel):
             if isinstance(self.optim, FlatAdamW):
                 self.optim.mean_scale = 1.0
             return
-        lo = getattr(self, "_early_lo", None)
-        timed = getattr(self, "time_allreduce", False) and self.device.type == "cuda"
+        lo = self._early_lo
+        timed = self.time_allreduce and self.device.type == "cuda"
         if late is None or lo is None or lo <= 0:
             if late is not None:
                 late()
@@ -755,8 +688,6 @@ class LarvaNet(BaseModel):
         end of the last weight-gradient kernel to the point where AdamW may start)."""
         if not on:
             return None
-        if not hasattr(self, "allreduce_events"):
-            self.allreduce_events = []
         ev = torch.cuda.Event(enable_timing=True)
         ev.record()
         return ev
@@ -804,10 +735,9 @@ class LarvaNet(BaseModel):
         # sync_loss=False hands back a 0-d device tensor instead so the host can run ahead (a copy:
         # the captured step's own loss tensor is overwritten by the next replay)
         if self.sync_loss:
-            how, self._loss_in_flight = getattr(self, "_loss_in_flight", False), False
-            if how == "event":   # (early-loss captures: see _forward_backward)
-                self._loss_done.synchronize()
-                return self._loss_host.item()
+            how, self._loss_in_flight = self._loss_in_flight, False
+            if how == "split":   # (early-loss captures: see CapturedStep.replay)
+                return self._handoffs["split"].result()
             if how == "poll":
                 return self._poll_loss()
             return loss.item()
@@ -819,7 +749,7 @@ class LarvaNet(BaseModel):
         sequence number, so a late store of an earlier replay is never taken for this one's (and a loss that IS NaN is
         just a value).  A short spin -- the loss is normally there within the forward's ~0.6 ms --, then the core is
         yielded between looks; after 5 s the stream is synchronised (the launch must then have stored)."""
-        cell = self._loss_cell
+        cell = self._handoffs["poll"]
         t0 = time.perf_counter()
         spins = 0
         while True:
@@ -883,76 +813,43 @@ class LarvaNet(BaseModel):
         return StepScope(defer_wgrad=False, joint_input_grads=False, dual_chain=self.dual_chain,
                          lazy_chain_joins=(True, False))
 
-    def _infer(self, x):
-        """self.model(x) without gradients.  A batch shape seen for the second time is captured into a
-        hipGraph (launched one by one from Python the ~36 kernels of a 16 x 3 x 48 x 48 forward are
-        host-bound: 0.70 ms against 0.5 ms of GPU time) and replayed from then on; shapes seen once --
-        validation images all differ in size -- run eagerly.  The returned tensor of a replay is the
-        graph's output buffer: callers that keep it across calls copy it (upscale() moves it to the
-        host anyway)."""
-        if torch.is_grad_enabled():
-            return self.model(x)
-        if not (self.use_hip_graph and x.is_cuda):
-            return self._forward_nograd(x)
+    def _eager_or_graph(self, x, form):
+        """The grad-free forward of the device batch `x` in `form`, eagerly or as a hipGraph: THE rule.  A shape seen for
+        the second time is captured (launched one by one from Python the ~36 kernels of a 16 x 3 x 48 x 48 forward are
+        host-bound: 0.70 ms against 0.5 ms of GPU time) and replayed from then on (infer_graphs.GraphTable; each table has
+        its own limit, so each path captures exactly what it would without the others).  A replay returns the graph's
+        output buffer: callers that keep it across calls copy it."""
+        n = int(x.shape[0])
+        h, w = (int(v) for v in (x.shape[1:3] if form.u8 else x.shape[2:4]))
         # A whole validation image is 36 launches of 60 us each: the host is ~2 ms ahead of the GPU after the first few,
         # and eager launches have no replay boundary and no copy into a static input: 2.162 against 2.178 ms per
-        # 339 x 510 image (tools/infer_modes.py, round 5).  The capture pays where the launches are short.
-        if is_large_inference(x.shape[0], x.shape[2], x.shape[3]):   # (the same rule picks the direct head kernel)
-            return self._forward_nograd(x)
-        return self._capture_or_run(x, False)
+        # 339 x 510 image (tools/infer_modes.py, round 5).  The capture pays where the launches are short.  The rule asks
+        # about the forward's own batch (the ensemble: 8 N slots of a square image, 4 N otherwise) and also picks the head kernel.
+        if not (self.use_hip_graph and x.is_cuda) or is_large_inference((8 if h == w else 4) * n if form.ensemble else n, h, w):
+            return self._forward_nograd(x, *form)
+        table = self._infer_graphs_se if form.ensemble else self._infer_graphs_u8 if form.u8 else self._infer_graphs
+        tag = ("u8" if form.u8 else "f32", "se") if form.ensemble else ("u8",) if form.u8 else ()
+        return table.forward((tuple(x.shape), self.precision) + tag, x, capture=lambda x: self._capture_infer(x, form),
+                             run=lambda x: self._forward_nograd(x, *form))
+
+    def _infer(self, x):
+        """self.model(x); without gradients, by _eager_or_graph."""
+        return self.model(x) if torch.is_grad_enabled() else self._eager_or_graph(x, Form())
 
     def _infer_u8(self, x_u8):
-        """_infer for the uint8 path [N][H][W][3], with the same rules.  Its graphs are kept under (shape, precision,
-        "u8") in a table of their own (_infer_graphs_u8, with its own limit of four), so the float path captures exactly
-        what it would without this one.  A replay returns the graph's output buffer."""
-        if not self.use_hip_graph or is_large_inference(x_u8.shape[0], x_u8.shape[1], x_u8.shape[2]):
-            return self._forward_nograd(x_u8, True)
-        return self._capture_or_run(x_u8, True)
+        """_infer for the uint8 path [N][H][W][3]."""
+        return self._eager_or_graph(x_u8, Form(u8=True))
 
     def _infer_ensemble(self, x, u8=False):
-        """The x8 self-ensemble of a device batch (uint8 [N][H][W][3] when u8, else float [N][3][H][W]) with _infer's
-        rules: the large-inference rule asks about each forward's batch (8 N slots of a square image, 4 N otherwise);
-        graphs are kept under (shape, precision, "u8" / "f32", "se") in a table of their own (_infer_graphs_se, its own
-        limit of four), so the plain float and uint8 paths capture exactly what they would without this one.  A captured
-        ensemble holds the input launch, the forward(s) and the merge launch."""
-        n = int(x.shape[0])
-        h, w = (int(v) for v in (x.shape[1:3] if u8 else x.shape[2:4]))
-        if not (self.use_hip_graph and x.is_cuda) or is_large_inference((8 if h == w else 4) * n, h, w):
-            return self._forward_nograd(x, u8, True)
-        return self._capture_or_run(x, u8, True)
+        """The x8 self-ensemble of a device batch: the graph holds the input launch, the forward(s) and the merge launch."""
+        return self._eager_or_graph(x, Form(u8, True))
 
     def _infer_u8_images(self, x_u8):
-        """What upscale_u8 / evaluate_u8_tensor and the streams (pipeline.py) run on a uint8 device batch: _infer_u8, or
-        under --self_ensemble the ensemble."""
-        return self._infer_ensemble(x_u8, True) if self._self_ensemble() else self._infer_u8(x_u8)
+        """What the streams (pipeline.py) run on a uint8 device batch: _infer_u8, or under --self_ensemble the ensemble."""
+        return self._eager_or_graph(x_u8, Form(True, self._self_ensemble()))
 
-    def _capture_or_run(self, x, u8, ensemble=False):
-        """The grad-free forward of a small device batch `x` (uint8 images when u8; the self-ensemble when ensemble): a
-        shape seen once runs eagerly; seen for the second time it is captured (at most four graphs per table; False
-        marks a capture that failed) and replayed from then on."""
-        table = "_se" if ensemble else ("_u8" if u8 else "")
-        cache = self.__dict__.setdefault("_infer_graphs" + table, {})
-        seen = self.__dict__.setdefault("_infer_seen" + table, {})
-        key = (tuple(x.shape), self._precision()) + (("u8",) if u8 else ())
-        if ensemble:
-            key = (tuple(x.shape), self._precision(), "u8" if u8 else "f32", "se")
-        ent = cache.get(key)
-        if ent is None:
-            if len(seen) > 512:   # (a long run over images of ever new sizes: forget the counts)
-                seen.clear()
-            seen[key] = seen.get(key, 0) + 1
-            if seen[key] < 2 or len(cache) >= 4:
-                return self._forward_nograd(x, u8, ensemble)
-            ent = cache[key] = self._capture_infer(x, u8, ensemble)
-        if ent is False:
-            return self._forward_nograd(x, u8, ensemble)
-        self._refresh_inference_weights()   # weights restored / stepped since the capture: repack (outside the graph)
-        static_x, graph, out = ent
-        static_x.copy_(x)
-        graph.replay()
-        return out
-
-    def _capture_infer(self, x, u8=False, ensemble=False):
+    def _capture_infer(self, x, form):
+        """-> replay(x) of the captured forward of x's shape in `form`, or False if the capture failed."""
         static_x = x.clone()
         try:
             side = torch.cuda.Stream()
@@ -960,13 +857,12 @@ class LarvaNet(BaseModel):
             with torch.cuda.stream(side):
                 for _ in range(2):
                     with self._infer_scope():
-                        self._forward_nograd(static_x, u8, ensemble)
+                        self._forward_nograd(static_x, *form)
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
                 with self._infer_scope():
-                    out = self._forward_nograd(static_x, u8, ensemble)
-            return static_x, graph, out
+                    out = self._forward_nograd(static_x, *form)
         except Exception as e:   # an optimisation only
             if self.strict_graph:
                 raise
@@ -975,17 +871,21 @@ class LarvaNet(BaseModel):
             torch.cuda.synchronize()
             return False
 
-    def _precision(self):
-        return getattr(self, "precision", "fp32")
+        def replay(x):
+            self._refresh_inference_weights()   # weights restored / stepped since the capture: repack (outside the graph)
+            static_x.copy_(x)
+            graph.replay()
+            return out
+        return replay
 
     def _half(self):
         """The fp16 forward when the model runs at --precision fp16, else None: the one place precision is decided."""
-        return self.model.half_forward() if self._precision() == "fp16" else None
+        return self.model.half_forward() if self.precision == "fp16" else None
 
     def _self_ensemble(self):
         """Does this model run the x8 self-ensemble in its image entry points (--self_ensemble)?  The one place it is
         decided; grad-enabled calls, test, fwd_runtime and the validation of training never ask."""
-        return bool(getattr(getattr(self, "args", None), "self_ensemble", False))
+        return bool(getattr(self.args, "self_ensemble", False))
 
     def _forward_ensemble(self, x, u8):
         """E(x) of image_utils.self_ensemble on the device (no graph): one launch builds the eight inputs as batch slots,
@@ -1047,16 +947,13 @@ class LarvaNet(BaseModel):
         half = self._half()
         return half is not None and half.take_overflow()
 
-    def _infer_checked(self, x, u8=False, ensemble=False):
-        """upscale / upscale_tensor / test and their uint8 forms: an fp16 activation that left the fp16 range is an
-        error, not a result.  ensemble: the caller is an image entry point of a model with --self_ensemble."""
+    def _infer_checked(self, x, u8=False, ensemble=None):
+        """test and the image entry points, all under no_grad: an fp16 activation that left the fp16 range is an error,
+        not a result.  ensemble None: as --self_ensemble says -- the one place the image entry points' form is decided."""
         half = self._half()
         if half is not None:
             half.clear_overflow()
-        if ensemble:
-            out = self._infer_ensemble(x, u8)
-        else:
-            out = self._infer_u8(x) if u8 else self._infer(x)
+        out = self._eager_or_graph(x, Form(u8, self._self_ensemble() if ensemble is None else ensemble))
         if self.fp16_overflowed():
             raise self.overflow_error()
         return out
@@ -1068,12 +965,12 @@ class LarvaNet(BaseModel):
     def upscale(self, input_list, scale):
         """list of CHW numpy images -> (N, 3, 4H, 4W) float32 numpy (models/LarvaNet.py:163-171)."""
         with torch.no_grad():
-            return self._infer_checked(self._to_input_tensor(input_list), ensemble=self._self_ensemble()).detach().cpu().numpy()
+            return self._infer_checked(self._to_input_tensor(input_list)).detach().cpu().numpy()
 
     def upscale_tensor(self, input_list):
         """upscale() without the trip to the host: (N, 3, 4H, 4W) float32 on self.device."""
         with torch.no_grad():
-            return self._infer_checked(self._to_input_tensor(input_list), ensemble=self._self_ensemble()).detach().clone()
+            return self._infer_checked(self._to_input_tensor(input_list)).detach().clone()
 
     # ------------------------------------------------------------------ 8-bit images in, 8-bit images out
     def _check_u8_images(self, input_list, scale):
@@ -1111,13 +1008,13 @@ class LarvaNet(BaseModel):
         with torch.no_grad():
             x = torch.from_numpy(batch).to(self.device)
             _require_hip(x)
-            return self._infer_checked(x, u8=True, ensemble=self._self_ensemble()).cpu().numpy()
+            return self._infer_checked(x, u8=True).cpu().numpy()
 
     def upscale_u8_tensor(self, x_u8):
         """upscale_u8 without the trips to and from the host: uint8 [N][H][W][3] on self.device -> uint8 [N][sH][sW][3]."""
         x = self._check_u8_tensor(x_u8)
         with torch.no_grad():
-            return self._infer_checked(x, u8=True, ensemble=self._self_ensemble()).clone()
+            return self._infer_checked(x, u8=True).clone()
 
     def evaluate_u8_tensor(self, x_u8, truth_u8, shave=None, channel="y", ssim=True):
         """Upscale and score on the device: x_u8 uint8 [N][H][W][3] and truth_u8 uint8 [N][th][tw][3] (th >= sH, tw >= sW,
@@ -1136,7 +1033,7 @@ class LarvaNet(BaseModel):
         _require_hip(x)
         _require_hip(truth)
         with torch.no_grad():
-            out = self._infer_checked(x, u8=True, ensemble=self._self_ensemble())
+            out = self._infer_checked(x, u8=True)
             records = torch.stack([K.u8_metrics(out[n], truth[n], shave, channel, ssim) for n in range(out.shape[0])])
         return [K.metrics_from_record(r) for r in records.cpu().numpy()]
 
@@ -1150,13 +1047,11 @@ class LarvaNet(BaseModel):
     def test(self, input_list):
         if torch.is_grad_enabled():
             return self.model(self._to_input_tensor(input_list))
-        return self._infer_checked(self._to_input_tensor(input_list)).clone()
+        return self._infer_checked(self._to_input_tensor(input_list), ensemble=False).clone()
 
     def fwd_runtime(self, input_tensor):
         """models/LarvaNet.py:200-202; under torch.no_grad() a repeated shape replays a captured graph and
         the result is that graph's output buffer (overwritten by the next call)."""
-        if torch.is_grad_enabled():
-            return self.model(input_tensor)
         return self._infer(input_tensor)
 
     # ------------------------------------------------------------------ checkpoints

@@ -1,8 +1,8 @@
 """Images in, images out, with the host link hidden behind the forward.
 
-upscale_stream() walks an iterable of uint8 (H, W, 3) images of any mix of sizes through model._infer_u8 (under
---self_ensemble: the device-side x8 ensemble, model._infer_u8_images decides) and yields the uint8 (sH, sW, 3) results in
-input order.  Image i+1's host-to-device copy and image i-1's device-to-host copy run on
+upscale_stream() walks an iterable of uint8 (H, W, 3) images of any mix of sizes through model._infer_u8_images (the
+uint8 form of the plugin's one grad-free dispatch; under --self_ensemble the device-side x8 ensemble) and yields the
+uint8 (sH, sW, 3) results in input order.  Image i+1's host-to-device copy and image i-1's device-to-host copy run on
 ONE extra stream beside image i's forward:
 
     copy stream     H2D(0) H2D(1) D2H(0) H2D(2) D2H(1) ...        (issue order; D2H(i) waits for forward i's event)

@@ -8,7 +8,7 @@ is written as <output_path>/<stem>.png.
 --self_ensemble (a model flag, like --precision) writes the geometric self-ensemble: the mean of the eight flips /
 transposes of each image run through the network and mapped back, merged on the device.
 
-The images stay 8-bit end to end (pipeline.upscale_stream over model._infer_u8): PNGs are decoded and encoded by a
+The images stay 8-bit end to end (pipeline.upscale_stream over model._infer_u8_images): PNGs are decoded and encoded by a
 thread pool around the stream, a quarter of the float path's bytes cross the host link, and the copies of neighbouring
 images run beside the forward.  Under torchrun file i goes to rank i mod world, as validate.py shards.  The
 reference's --chop_forward is not carried over (approximate by design; image_utils has exact bands)."""

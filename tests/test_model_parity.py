@@ -443,7 +443,7 @@ def test_early_loss_capture_trains_exactly_like_the_single_graph(hip_device, nam
         m = _model(name, flags, training=True, seed=5)
         m.early_loss, m.sync_loss = early, sync
         losses = [m.train_step_larva(args, FakeValLoader(7), x, t) for x, t in zip(xs, ts)]
-        assert (m._graph_back is not None) == (early == "split" and sync) and m._graph_polls == (early == "poll" and sync)
+        assert (m._step.back is not None) == (early == "split" and sync) and (m._step.mode == "poll") == (early == "poll" and sync)
         if sync:
             assert all(isinstance(v, float) for v in losses)
         else:
@@ -476,7 +476,7 @@ def test_other_interpolate_modes_against_the_cpu_restatement(hip_device, name, m
     t = torch.from_numpy(rng.randint(0, 256, size=(2, 3, 48, 48)).astype(np.float32))
     for use_graph in (False, True):
         m.use_hip_graph = use_graph
-        m._graph_shape = None
+        m._step = None
         loss, _ = m._forward_backward(x.to(hip_device), t.to(hip_device))
         torch.cuda.synchronize()
         sd_req = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
@@ -525,7 +525,7 @@ def test_repeated_inference_shape_replays_a_graph_with_the_eager_result(hip_devi
     rng = np.random.RandomState(5)
     batch = [rng.randint(0, 256, size=(3, 16, 20)).astype(np.float32) for _ in range(4)]
     eager = m.upscale(batch, 4)                       # first sight: eager
-    assert not getattr(m, "_infer_graphs", None)
+    assert not m._infer_graphs
     second = m.upscale(batch, 4)                      # second sight: captured + replayed
     assert len(m._infer_graphs) == 1 and all(v is not False for v in m._infer_graphs.values())
     third = m.upscale(batch, 4)

@@ -276,7 +276,7 @@ def test_eager_capture_replay_agree_and_the_plain_paths_capture_what_they_did(hi
         assert np.array_equal(plain.upscale([_chw(a)], 4), want)
     assert set(plain._infer_graphs_u8) == {((1, 9, 14, 3), precision, "u8")}
     assert set(plain._infer_graphs) == {((1, 3, 9, 14), precision)}
-    assert not hasattr(plain, "_infer_graphs_se") and not hasattr(plain, "_infer_seen_se")
+    assert not plain._infer_graphs_se and not plain._infer_graphs_se.seen
     # test / fwd_runtime never ensemble
     with torch.no_grad():
         x = torch.from_numpy(_chw(a)[None]).to(hip_device)

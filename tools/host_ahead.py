@@ -48,7 +48,7 @@ for label in ("as is",):
     torch.cuda.synchronize()
     total = time.perf_counter() - t0
     a = time.perf_counter()
-    model._graph.replay()
+    model._step.graph.replay()
     r = time.perf_counter() - a
     torch.cuda.synchronize()
     print("dual_chain=%s: host issue per step median %.0f us (min %.0f max %.0f), all 20 issued after %.2f ms, GPU done after %.2f ms "
