@@ -406,6 +406,32 @@ int larva_dihedral_inputs_f32(const float* in, float* a, float* b, int N, int H,
 int larva_dihedral_mean(const float* a, const float* b, float* out_f32, unsigned char* out_u8, int N, int H, int W,
                         void* stream);
 
+/* ---- bicubic decimation of uint8 images (csrc/larva_downscale.hip) -------------------------------------
+ * The degradation SR inputs are made with: antialiased bicubic decimation by s = 2, 3 or 4 in the MATLAB imresize
+ * convention, exact in integers.  Output h = H / s, w = W / s (floor, both >= 1); only the top-left h s x w s pixels are
+ * read.  Along an axis output i takes inputs j = s i + o with integer weights over D,
+ *   s = 2: D = 256,  o = -3..4:  -3 -9 29 111 111 29 -9 -3
+ *   s = 3: D = 81,   o = -4..6:  -1 -2 0 9 21 27 21 9 0 -2 -1
+ *   s = 4: D = 4096, o = -6..9:  -7 -45 -75 -49 93 399 745 987 987 745 399 93 -49 -75 -45 -7
+ * (the Keys cubic, a = -1/2, c((u - j) / s) / s at u = (i + 1/2) s - 1/2); j outside [0, n), n the cropped length, reflects:
+ * m = j mod 2 n, j' = m < n ? m : 2 n - 1 - m.  out = clip(round_half_even(N / D^2), 0, 255), N the exact integer double
+ * sum: one rounding, at the end.  image_utils.bicubic_downscale_u8 is the same on the host, byte for byte.
+ *
+ * larva_bicubic_down_u8: one image, src uint8 HWC with `pitch` >= 3 W bytes per row (any pitch and any alignment: a
+ * window into a larger image), dst uint8 [h][w][3] contiguous.  One launch.
+ *
+ * larva_bicubic_down_u8_table: n images of a byte table in ONE launch.  Image i is at data + offsets[i] with (H, W) =
+ * hw[2 i], hw[2 i + 1] (device arrays, as larva_gather_patches takes them) and goes to out + out_offsets[i]; planar == 0:
+ * HWC images [H][W][3] -> [h][w][3]; planar != 0: CHW images [3][H][W] (the sampler's tables) -> [3][h][w], every plane
+ * an image of its own.  The grid is flat: tile_prefix (device, int [n + 1]) holds the workgroups of the images before i,
+ * image i having planes * ceil(h / 8) * ceil(w / (planar ? 96 : 32)) of them (planes = planar ? 3 : 1), and total_tiles =
+ * tile_prefix[n].  Bytes of `out` outside the images are not touched. */
+int larva_bicubic_down_u8(const unsigned char* src, int H, int W, long long pitch, int s, unsigned char* dst,
+                          void* stream);
+int larva_bicubic_down_u8_table(const unsigned char* data, const long long* offsets, const int* hw, int n, int s,
+                                int planar, unsigned char* out, const long long* out_offsets, const int* tile_prefix,
+                                int total_tiles, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

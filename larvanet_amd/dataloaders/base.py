@@ -35,6 +35,12 @@ class BaseLoader:
         """-> (LR image, HR image, image name)"""
         raise NotImplementedError
 
+    def get_truth_image(self, image_index, scale):
+        """-> (HR image, image name) without touching the LR image where a loader can (device_patch_loader
+        --lr_from_hr makes the LR images itself)."""
+        _, hr, name = self.get_image_pair(image_index, scale)
+        return hr, name
+
     # threaded loaders only
     def start_training_queue_runner(self, batch_size, input_patch_size):
         raise NotImplementedError

@@ -11,7 +11,13 @@ div2k_train_loader; `synthetic_loader` for tests and benchmarks).
 Data parallel start-up is O(1) in the world size: RANK 0 decodes the dataset once (a thread pool over the source's
 get_image_pair: PIL's PNG decoder releases the GIL) and the uint8 image tables + offset / size tables are BROADCAST to the
 other ranks' HBM (dist.broadcast_tensor: RCCL over xGMI, ~5 GB once) -- eight ranks of one host do not decode 800 PNG
-pairs eight times.  Every rank keeps its own draw stream (seed + 1000 rank)."""
+pairs eight times.  Every rank keeps its own draw stream (seed + 1000 rank).
+
+--lr_from_hr: the source hands out the HR images alone (get_truth_image: div2k_train_loader then needs no LR folder).
+Per scale the HR images are cropped top-left to multiples of the scale, uploaded and broadcast as above, and every
+rank makes its own LR table from its HR table with one launch per scale (kernels.bicubic_down_u8_table: bicubic
+decimation in the MATLAB imresize convention, exact in integers, so the tables of all ranks are identical without a
+broadcast).  Draw order, shapes and get_device_batch are the same."""
 import argparse
 import copy
 import importlib
@@ -59,12 +65,32 @@ def decode_workers():
     return max(1, min(32, int(os.environ.get("LARVA_DECODE_THREADS", ldist.host_threads()))))
 
 
-def build_host_tables(source, scales, workers=1):
+def build_host_tables(source, scales, workers=1, lr_from_hr=False):
     """Decode every image pair of `source` once -> ({scale: {"lr", "hr": uint8 [bytes], "lr_off", "hr_off": int64 [n],
     "lr_hw", "hr_hw": int32 [2n]}}, [(lr_h, lr_w)] of the first scale).  Images are rounded / clipped to uint8 exactly as
-    the sampler's kernel expects them (PNG sources are uint8-valued already).  Host only: runs on rank 0."""
+    the sampler's kernel expects them (PNG sources are uint8-valued already).  Host only: runs on rank 0.
+    lr_from_hr: only the HR images are decoded (source.get_truth_image), cropped top-left to multiples of the scale; the
+    tables hold the "hr" entries alone and the shapes are those of the LR images to be made (make_lr_tables)."""
     n = source.get_num_images()
     shapes, tables = [], {}
+    if lr_from_hr:
+        for scale in scales:
+            def truth(i, scale=scale):
+                hr, _ = source.get_truth_image(i, scale)
+                h, w = K.bicubic_down_size(hr.shape[1], hr.shape[2], scale)
+                return np.ascontiguousarray(np.clip(np.round(hr[:, :h * scale, :w * scale]), 0, 255).astype(np.uint8))
+            if workers > 1 and n > 1:
+                with ThreadPoolExecutor(max_workers=workers) as pool:
+                    images = list(pool.map(truth, range(n)))
+            else:
+                images = [truth(i) for i in range(n)]
+            hr_off = np.zeros(n, np.int64)
+            hr_off[1:] = np.cumsum([a.size for a in images])[:-1]
+            tables[scale] = {"hr": np.concatenate([a.ravel() for a in images]), "hr_off": hr_off,
+                             "hr_hw": np.asarray([d for a in images for d in a.shape[1:]], np.int32)}
+            if scale == scales[0]:
+                shapes = [(a.shape[1] // scale, a.shape[2] // scale) for a in images]
+        return tables, shapes
     for scale in scales:
         def one(i, scale=scale):
             lr, hr, _ = source.get_image_pair(i, scale)
@@ -105,11 +131,24 @@ def share_tables(host_tables, shapes, scales, device):
     out = {}
     for s in scales:
         out[s] = {}
-        for k in ("lr", "hr", "lr_off", "hr_off", "lr_hw", "hr_hw"):
+        for k in sizes[s]:   # (rank 0's keys, in its order: all six, or the "hr" three under --lr_from_hr)
             t = (torch.from_numpy(host_tables[s][k]).to(device) if main
                  else torch.empty(sizes[s][k], dtype=TABLE_DTYPES[k], device=device))
             out[s][k] = ldist.broadcast_tensor(t, src=0)
     return out, [tuple(hw) for hw in shapes]
+
+
+def make_lr_tables(tables, device):
+    """The "lr" entries of tables that hold only "hr" ones (--lr_from_hr): per scale one launch decimates every CHW image
+    of the HR table into a new LR table."""
+    for scale, t in tables.items():
+        hw = t["hr_hw"].cpu().numpy().reshape(-1, 2)
+        lr_off, lr_hw, nbytes = K.bicubic_down_table_layout([(int(H), int(W)) for H, W in hw], scale)
+        t["lr_off"] = torch.from_numpy(lr_off).to(device)
+        t["lr_hw"] = torch.from_numpy(lr_hw).to(device)
+        t["lr"] = K.bicubic_down_u8_table(t["hr"], t["hr_off"], t["hr_hw"], scale,
+                                          torch.empty(nbytes, dtype=torch.uint8, device=device), t["lr_off"], planar=True)
+    return tables
 
 
 class DevicePatchLoader(BaseLoader):
@@ -120,6 +159,9 @@ class DevicePatchLoader(BaseLoader):
         parser.add_argument("--device_source", type=str, default="div2k_train_loader",
                             help="loader plugin that supplies the images to make resident")
         parser.add_argument("--data_seed", type=int, default=None)
+        parser.add_argument("--lr_from_hr", action="store_true",
+                            help="decode the HR images alone and make the LR tables on the device (bicubic, MATLAB "
+                                 "convention): the source needs no LR images")
         self.args, remaining = parser.parse_known_args(args=args)
         self.source = importlib.import_module("larvanet_amd.dataloaders." + self.args.device_source).create_loader()
         src_args, remaining = self.source.parse_args(remaining)
@@ -137,10 +179,12 @@ class DevicePatchLoader(BaseLoader):
         seed = self.args.data_seed
         self.rng = np.random.RandomState(None if seed is None else ldist.seed_for_rank(seed))
         # decode once (rank 0, thread pool), broadcast to the other ranks' HBM
-        host, shapes = (build_host_tables(self.source, scales, decode_workers())
+        host, shapes = (build_host_tables(self.source, scales, decode_workers(), lr_from_hr=self.args.lr_from_hr)
                         if (ldist.is_main() or not ldist.active()) else (None, None))
         self.tables, self.shapes = share_tables(host, shapes, scales, self.device)
         del host
+        if self.args.lr_from_hr:
+            make_lr_tables(self.tables, self.device)
         n = len(self.shapes)
         print("data: %d image pairs resident on %s (%.1f MB)" % (
             n, self.device, sum(t["lr"].numel() + t["hr"].numel() for t in self.tables.values()) / 1e6))

@@ -87,6 +87,10 @@ class DIV2KLoader(BaseLoader):
         hr = self._image(("hr", name), os.path.join(self.args.data_truth_path, "%s.png" % name))
         return lr, hr, name
 
+    def get_truth_image(self, image_index, scale):
+        name = self.image_name_list[image_index]
+        return self._image(("hr", name), os.path.join(self.args.data_truth_path, "%s.png" % name)), name
+
     def get_image_patch_pair(self, image_index, scale, input_patch_size):
         lr, hr, _ = self.get_image_pair(image_index=image_index, scale=scale)
         return augment_pair(self.rng, lr, hr, scale, input_patch_size)

@@ -4,6 +4,11 @@ low-resolution input of --input_path, upscaled, and scored on the device: PSNR a
     python -m larvanet_amd.evaluate --model=LarvaNet --num_modules=4 --num_blocks=4,4,4,4 --restore_path=model.pth \\
         --input_path=LR --truth_path=HR [--output_path=SR] [--channel y|rgb] [--shave N] [--no_ssim] [--log FILE]
         [--precision fp16] [--self_ensemble] [--io_threads 8] [--depth 2]
+    python -m larvanet_amd.evaluate ... --truth_path=HR --lr_from_truth        (no LR folder: --input_path is ignored)
+
+--lr_from_truth makes every input on the device from its truth image: the bicubic decimation by --scale in the MATLAB
+imresize convention (kernels.bicubic_down_u8), the degradation SR benchmarks are prepared with.  The results equal
+those over the folder `python -m larvanet_amd.downscale_images --suffix` writes.
 
 --self_ensemble (a model flag, like --precision) scores the geometric self-ensemble, the "+" column of SR tables: the
 mean of the eight flips / transposes of each image run through the network and mapped back, merged on the device.
@@ -38,6 +43,8 @@ def build_parser():
     p.add_argument("--restore_global_step", type=int, default=0)
     p.add_argument("--input_path", type=str, default="LR")
     p.add_argument("--truth_path", type=str, default="HR")
+    p.add_argument("--lr_from_truth", action="store_true",
+                   help="make each input from its truth image on the device (bicubic, MATLAB convention); ignores --input_path")
     p.add_argument("--output_path", type=str, default=None, help="where to write the upscaled images; omitted = nowhere")
     p.add_argument("--channel", type=str, default="y", choices=("y", "rgb"),
                    help="y: BT.601 luma plane; rgb: the three colour planes (SSIM: their mean)")
@@ -80,7 +87,10 @@ def main(argv=None):
         raise ValueError("larvanet_amd.evaluate: --shave must be >= 0")
     rank, world = ldist.init_from_env()
     ldist.limit_host_threads()
-    pairs = pair_files(list_pngs(args.truth_path), list_pngs(args.input_path), args.scale)
+    if args.lr_from_truth:
+        pairs = [(name, None) for name in list_pngs(args.truth_path)]
+    else:
+        pairs = pair_files(list_pngs(args.truth_path), list_pngs(args.input_path), args.scale)
     print("data: %d images are prepared" % len(pairs))
     mine = shard(pairs, rank, world)
     if args.output_path is not None:
@@ -113,7 +123,8 @@ def main(argv=None):
         writes = collections.deque()
 
         def read_pair(names):
-            return read_rgb(os.path.join(args.input_path, names[1])), read_rgb(os.path.join(args.truth_path, names[0]))
+            truth = read_rgb(os.path.join(args.truth_path, names[0]))
+            return (None if names[1] is None else read_rgb(os.path.join(args.input_path, names[1]))), truth
 
         begin = time.perf_counter()
         with concurrent.futures.ThreadPoolExecutor(max_workers=threads) as pool:

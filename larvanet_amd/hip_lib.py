@@ -155,6 +155,11 @@ SIGNATURES = {
                                                  ctypes.c_int, ctypes.c_void_p]),
     "larva_dihedral_mean": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int, ctypes.c_void_p]),
+    "larva_bicubic_down_u8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int,
+                                             ctypes.c_void_p, ctypes.c_void_p]),
+    "larva_bicubic_down_u8_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                   ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
 }
 
 _lib = None

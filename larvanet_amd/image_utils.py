@@ -3,8 +3,64 @@ overlapping quadrants, each is upscaled on its own and the results are stitched 
 boundaries.  This is approximate by design (overlap/2 = 10 LR px is less than the network's
 receptive-field radius of 35) and is reproduced as is.
 
-Also the definitions of the geometric self-ensemble (--self_ensemble): the eight flips / transposes of the square."""
+Also the definitions of the geometric self-ensemble (--self_ensemble): the eight flips / transposes of the square, and
+of the bicubic decimation the low-resolution images of SR benchmarks are made with (bicubic_downscale_u8)."""
 import numpy as np
+
+# Bicubic decimation by an integer scale: scale -> (D, first offset, integer numerators).  Output i of an axis takes
+# input s i + first offset + k with weight numerators[k] / D = c((u - j) / s) / s at u = (i + 1/2) s - 1/2, c the Keys
+# cubic with a = -1/2 (the weights of a pixel sum to 1).  The one table kernels.bicubic_down_u8's checks and the host
+# restatement below read; csrc/larva_downscale.hip carries the same numbers (include/larva_hip.h lists them).
+BICUBIC_DOWN_TAPS = {
+    2: (256, -3, (-3, -9, 29, 111, 111, 29, -9, -3)),
+    3: (81, -4, (-1, -2, 0, 9, 21, 27, 21, 9, 0, -2, -1)),
+    4: (4096, -6, (-7, -45, -75, -49, 93, 399, 745, 987, 987, 745, 399, 93, -49, -75, -45, -7)),
+}
+
+
+def bicubic_down_size(height, width, scale):
+    """(h, w) = (height // scale, width // scale) of the decimated image; ValueError for a scale other than 2, 3, 4 or
+    an image smaller than one output pixel."""
+    if scale not in BICUBIC_DOWN_TAPS:
+        raise ValueError("larvanet_amd: bicubic downscaling takes scale 2, 3 or 4, got %r" % (scale,))
+    h, w = int(height) // int(scale), int(width) // int(scale)
+    if h < 1 or w < 1:
+        raise ValueError("larvanet_amd: a %d x %d image is smaller than one pixel at x%d" % (height, width, scale))
+    return h, w
+
+
+def _decimate_axis0(a, scale):
+    """Exact integer FIR with stride `scale` along axis 0 of the int64 array a (length a multiple of scale), indices
+    reflected symmetrically: m = j mod 2 n, j' = m if m < n else 2 n - 1 - m."""
+    _, first, taps = BICUBIC_DOWN_TAPS[scale]
+    n = a.shape[0]
+    j = scale * np.arange(n // scale)[:, None] + first + np.arange(len(taps))[None, :]
+    m = np.mod(j, 2 * n)
+    j = np.where(m < n, m, 2 * n - 1 - m)
+    out = np.zeros((n // scale,) + a.shape[1:], np.int64)
+    for k, t in enumerate(taps):
+        if t:
+            out += np.int64(t) * a[j[:, k]]
+    return out
+
+
+def bicubic_downscale_u8(image, scale):
+    """uint8 (H, W, 3) -> uint8 (H // scale, W // scale, 3): antialiased bicubic decimation in the MATLAB imresize
+    convention of the top-left (H // scale) scale x (W // scale) scale pixels, in exact integers with ONE rounding at the
+    end: clip(round_half_even(N / D^2), 0, 255).  The host restatement kernels.bicubic_down_u8 equals byte for byte."""
+    if not isinstance(image, np.ndarray) or image.dtype != np.uint8:
+        raise TypeError("larvanet_amd: bicubic_downscale_u8 takes a uint8 numpy array, got %s"
+                        % (getattr(image, "dtype", type(image).__name__),))
+    if image.ndim != 3 or image.shape[2] != 3:
+        raise ValueError("larvanet_amd: bicubic_downscale_u8 takes an (H, W, 3) image, got shape %s" % (image.shape,))
+    h, w = bicubic_down_size(image.shape[0], image.shape[1], scale)
+    d2 = BICUBIC_DOWN_TAPS[scale][0] ** 2
+    a = image[:h * scale, :w * scale].astype(np.int64)
+    a = _decimate_axis0(a, scale)                                         # rows
+    a = np.swapaxes(_decimate_axis0(np.swapaxes(a, 0, 1), scale), 0, 1)   # columns
+    q, r = np.floor_divide(a, d2), np.mod(a, d2)                          # floor semantics: 0 <= r < D^2
+    q = q + ((2 * r > d2) | ((2 * r == d2) & (q % 2 == 1)))
+    return np.clip(q, 0, 255).astype(np.uint8)
 
 
 def dihedral(a, t, axes=(0, 1)):

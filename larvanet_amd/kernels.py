@@ -1153,3 +1153,99 @@ def metrics_from_record(record):
     sums = r.view(np.float64)[1:1 + planes]
     ssim = None if count == 0 else float(sum(float(v) / count for v in sums) / planes)
     return {"psnr": psnr_from_sse(sse, n), "ssim": ssim, "sse": sse, "n": n}
+
+
+# ------------------------------------------------------------------ bicubic decimation (csrc/larva_downscale.hip)
+DOWN_TILE_ROWS = 8     # a workgroup's tile: 8 output rows x 96 output bytes (kDownRows / kDownBytes of the kernel)
+DOWN_TILE_BYTES = 96
+
+
+def bicubic_down_size(height, width, scale):
+    """(h, w) of the decimated image; ValueError for a scale other than 2, 3, 4 or less than one output pixel."""
+    from .image_utils import bicubic_down_size as size
+    return size(height, width, scale)
+
+
+def bicubic_down_u8(x_u8_hwc, scale, out=None):
+    """uint8 [H][W][3] on the device -> uint8 [H // scale][W // scale][3]: the bicubic decimation of SR data preparation
+    (image_utils.bicubic_downscale_u8, byte for byte), scale 2, 3 or 4, in one launch.  x may be a window into a larger
+    image: pixels contiguous (strides (pitch, 3, 1) with pitch >= 3 W), any pitch and offset.  `out`: a contiguous uint8
+    [h][w][3] tensor to fill."""
+    lib = hip_lib.load()
+    x = x_u8_hwc
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("larvanet_amd: x must be a uint8 tensor, got %s" % type(x).__name__)
+    if x.dtype != torch.uint8:
+        raise TypeError("larvanet_amd: x must be a uint8 tensor, got %s" % x.dtype)
+    if x.dim() != 3 or int(x.shape[2]) != 3:
+        raise ValueError("larvanet_amd: x must be [H][W][3], got %s" % (tuple(x.shape),))
+    H, W = int(x.shape[0]), int(x.shape[1])
+    h, w = bicubic_down_size(H, W, scale)
+    if not x.is_cuda:
+        raise RuntimeError("larvanet_amd: x must be a tensor on a HIP device (no CPU path exists)")
+    pitch = 3 * W if H == 1 else int(x.stride(0))
+    if int(x.stride(2)) != 1 or int(x.stride(1)) != 3 or pitch < 3 * W:
+        raise RuntimeError("larvanet_amd: x must have contiguous pixels and rows that do not overlap (strides %s)"
+                           % (tuple(x.stride()),))
+    if out is None:
+        out = torch.empty((h, w, 3), device=x.device, dtype=torch.uint8)
+    else:
+        _chk_u8_image(out, "out")
+        if tuple(out.shape) != (h, w, 3) or out.device != x.device:
+            raise RuntimeError("larvanet_amd: out must be [%d][%d][3] on the input's device, got %s"
+                               % (h, w, tuple(out.shape)))
+    hip_lib.check(lib.larva_bicubic_down_u8(x.data_ptr(), H, W, pitch, int(scale), out.data_ptr(), _stream()),
+                  "larva_bicubic_down_u8")
+    return out
+
+
+def bicubic_down_table_layout(shapes, scale):
+    """(H, W) per image -> (offsets int64 [n], hw int32 [2 n], bytes) of the table of their 3-channel decimated images
+    laid end to end (either channel order)."""
+    import numpy as np
+    sizes = [bicubic_down_size(H, W, scale) for H, W in shapes]
+    offsets = np.zeros(len(sizes), np.int64)
+    offsets[1:] = np.cumsum([3 * h * w for h, w in sizes])[:-1]
+    return offsets, np.asarray([d for hw in sizes for d in hw], np.int32), int(sum(3 * h * w for h, w in sizes))
+
+
+def bicubic_down_u8_table(data, offsets, hw, scale, out, out_offsets, planar=False):
+    """Every image of a uint8 table on the device decimated in ONE launch: image i at data[offsets[i]:] with (H, W) =
+    hw[2 i], hw[2 i + 1] (gather_patches' arguments) -> out[out_offsets[i]:], each equal to bicubic_down_u8 of that image.
+    planar=False: HWC images [H][W][3] -> [h][w][3]; planar=True: the sampler's CHW images [3][H][W] -> [3][h][w].  Bytes of
+    `out` outside the images stay as they are.  The four small tables are read back once to check every image against
+    both byte tables and to cut the flat grid (a dataset is prepared once); returns `out`."""
+    import numpy as np
+    lib = hip_lib.load()
+    for t, name, dt in ((data, "data", torch.uint8), (offsets, "offsets", torch.int64), (hw, "hw", torch.int32),
+                        (out, "out", torch.uint8), (out_offsets, "out_offsets", torch.int64)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise TypeError("larvanet_amd: %s must be a %s tensor" % (name, dt))
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError("larvanet_amd: %s must be a contiguous 1-D tensor, got %s" % (name, tuple(t.shape)))
+        if not t.is_cuda or t.device != data.device:
+            raise RuntimeError("larvanet_amd: %s must be on the HIP device of the table (no CPU path exists)" % name)
+    n = int(offsets.numel())
+    if n < 1 or int(hw.numel()) != 2 * n or int(out_offsets.numel()) != n:
+        raise ValueError("larvanet_amd: %d offsets need %d sizes and %d output offsets" % (n, 2 * n, n))
+    src_off, dst_off, sizes = offsets.cpu().numpy(), out_offsets.cpu().numpy(), hw.cpu().numpy().reshape(n, 2)
+    per_row = DOWN_TILE_BYTES if planar else DOWN_TILE_BYTES // 3
+    prefix, spans = np.zeros(n + 1, np.int64), []
+    for i, (H, W) in enumerate(sizes):
+        h, w = bicubic_down_size(int(H), int(W), scale)
+        if src_off[i] < 0 or src_off[i] + 3 * int(H) * int(W) > data.numel():
+            raise ValueError("larvanet_amd: image %d lies outside the source table" % i)
+        if dst_off[i] < 0 or dst_off[i] + 3 * h * w > out.numel():
+            raise ValueError("larvanet_amd: image %d lies outside the destination table" % i)
+        spans.append((int(dst_off[i]), int(dst_off[i]) + 3 * h * w))
+        prefix[i + 1] = prefix[i] + (3 if planar else 1) * (-(-h // DOWN_TILE_ROWS)) * (-(-w // per_row))
+    spans.sort()
+    if any(a[1] > b[0] for a, b in zip(spans, spans[1:])):
+        raise ValueError("larvanet_amd: decimated images overlap in the destination table")
+    if prefix[n] >= 2 ** 31:
+        raise ValueError("larvanet_amd: too many tiles for one launch (%d)" % prefix[n])
+    tiles = torch.from_numpy(prefix.astype(np.int32)).to(data.device)
+    hip_lib.check(lib.larva_bicubic_down_u8_table(data.data_ptr(), offsets.data_ptr(), hw.data_ptr(), n, int(scale),
+                                                  int(bool(planar)), out.data_ptr(), out_offsets.data_ptr(), tiles.data_ptr(),
+                                                  int(prefix[n]), _stream()), "larva_bicubic_down_u8_table")
+    return out

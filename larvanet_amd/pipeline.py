@@ -16,7 +16,9 @@ the copy stream.  A slot is reused only after its device-to-host copy has been w
 
 evaluate_stream() is the same pipeline over (input, truth) pairs: the truth image travels in on the copy stream beside
 the input, the metric launch (kernels.u8_metrics) follows the forward on the compute stream, and only the 64-byte result
-record comes back unless the images are kept.
+record comes back unless the images are kept.  A pair whose input is None has it made from the truth on the device
+(kernels.bicubic_down_u8 on the compute stream, between the truth's arrival and the forward): no LR image is read,
+pinned or copied.
 """
 import collections
 
@@ -56,6 +58,12 @@ class _Slot:
         self.pin_in = self._grown(self.pin_in, n, True)
         self.dev_in = self._grown(self.dev_in, n, False)
         return self.pin_in[:n].view(shape), self.dev_in[:n].view(shape)
+
+    def view_made_in(self, shape):
+        """The device input buffer alone: an input made on the device has no host side."""
+        n = int(np.prod(shape))
+        self.dev_in = self._grown(self.dev_in, n, False)
+        return self.dev_in[:n].view(shape)
 
     def views_truth(self, shape):
         n = int(np.prod(shape))
@@ -108,7 +116,10 @@ def evaluate_stream(model, pairs, scale, shave=None, channel="y", ssim=True, dep
     tuple (dict, upscaled uint8 image).  upscale_stream's pipeline: the truth goes in beside the input, the metrics run
     behind the forward, the record (and the image only when kept) comes back.  A pair no metric is defined for (truth
     smaller than the output, window below 11 pixels with SSIM) raises ValueError before anything of it is launched; fp16
-    overflow raises at the image's turn."""
+    overflow raises at the image's turn.  A pair (None, truth) is scored on lr = the bicubic decimation of the truth by
+    `scale`, made on the device (kernels.bicubic_down_u8: the truth's top-left (H // scale) scale x (W // scale) scale
+    pixels, the window the metrics crop to anyway); its result equals the pair (image_utils.bicubic_downscale_u8(truth,
+    scale), truth)'s."""
     from . import kernels as K
     depth = int(depth)
     if depth < 1:
@@ -173,27 +184,38 @@ def _stream(model, images, depth, score=None):
                     _check_image(image)
                 else:
                     image, truth = image
-                    _check_image(image, "evaluate_stream")
                     _check_image(truth, "evaluate_stream")
-                    K.metric_window((model.scale * image.shape[0], model.scale * image.shape[1]), truth.shape,
+                    if image is None:   # the input is made from the truth on the device
+                        in_shape = K.bicubic_down_size(truth.shape[0], truth.shape[1], model.scale) + (3,)
+                    else:
+                        _check_image(image, "evaluate_stream")
+                        in_shape = tuple(image.shape)
+                    K.metric_window((model.scale * in_shape[0], model.scale * in_shape[1]), truth.shape,
                                     score["shave"], score["ssim"])
                 if len(inflight) == depth:
                     yield retire(inflight.popleft())
                 slot = free.pop()
-                shape = (1,) + tuple(image.shape)
-                pin_in, dev_in = slot.views_in(shape)
-                np.copyto(pin_in.numpy()[0], image)
+                made = score is not None and image is None
+                shape = (1,) + (in_shape if made else tuple(image.shape))
+                if made:
+                    dev_in = slot.view_made_in(shape)
+                else:
+                    pin_in, dev_in = slot.views_in(shape)
+                    np.copyto(pin_in.numpy()[0], image)
                 if score is not None:
                     pin_truth, dev_truth = slot.views_truth(tuple(truth.shape))
                     np.copyto(pin_truth.numpy(), truth)
                 with torch.cuda.stream(copy):
-                    dev_in.copy_(pin_in, non_blocking=True)
+                    if not made:
+                        dev_in.copy_(pin_in, non_blocking=True)
                     if score is not None:
                         dev_truth.copy_(pin_truth, non_blocking=True)
                     slot.h2d.record(copy)
                 if inflight:   # the previous image's way back, queued behind this image's way in
                     issue_d2h(inflight[-1])
                 compute.wait_event(slot.h2d)
+                if made:
+                    K.bicubic_down_u8(dev_truth, model.scale, out=dev_in[0])
                 out = model._infer_u8_images(dev_in)   # (the x8 self-ensemble under --self_ensemble)
                 slot.out_shape = tuple(out.shape)
                 if keep:
