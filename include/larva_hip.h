@@ -389,6 +389,26 @@ int larva_f16_conv3x3_shuffle_base(const uint16_t* src, const uint16_t* wpk, con
 int larva_f16_conv3x3_shuffle_base_u8(const uint16_t* src, const uint16_t* wpk, const float* bias, const float* base,
                                       unsigned char* out, unsigned* flag, int N, int H, int W, void* stream);
 
+/* Job launches: njobs (1..8) independent single-source 48 -> 48 convs of ONE shape in one grid -- the legs of a multi-exit
+ * network once the bodies have run.  srcs, wpks, biases and outs are host arrays of njobs device pointers (job j reads
+ * srcs[j], wpks[j], biases[j] and writes outs[j]); every pointer must be non-NULL.  Job j stores bit for bit what the
+ * single-job entry point stores for its operands: a workgroup runs the same tile code after looking its job up from its
+ * block index.  larva_f16_conv3x3_jobs: + bias, then ReLU if relu != 0, rounded once to fp16 (larva_f16_conv3x3 with one
+ * source and no residual): the legs' first conv. */
+int larva_f16_conv3x3_jobs(int njobs, const uint16_t* const* srcs, const uint16_t* const* wpks,
+                           const float* const* biases, int relu, uint16_t* const* outs, unsigned* flag, int N, int H,
+                           int W, void* stream);
+
+/* The leg end of every job against ONE shared fp32 base image [N][3][4H][4W]: exactly one of outs_f32 (njobs fp32
+ * [N][3][4H][4W] images, larva_f16_conv3x3_shuffle_base per job) and outs_u8 (njobs uint8 [N][4H][4W][3] images,
+ * larva_f16_conv3x3_shuffle_base_u8 per job; needs flag) is given, the other is NULL.  Both job entry points return
+ * hipErrorInvalidValue before any launch for njobs outside 1..8, a NULL pointer in an array, both or neither output
+ * array, or a shape whose grid (njobs times the tiles rounded up to a multiple of 8) does not fit. */
+int larva_f16_conv3x3_shuffle_base_jobs(int njobs, const uint16_t* const* srcs, const uint16_t* const* wpks,
+                                        const float* const* biases, const float* base, float* const* outs_f32,
+                                        unsigned char* const* outs_u8, unsigned* flag, int N, int H, int W,
+                                        void* stream);
+
 /* ---- geometric self-ensemble (--self_ensemble; csrc/larva_ensemble.hip) ------------------------------
  * dihedral(a, t), t = 0..7, over the spatial axes: reverse rows if t & 1, then reverse columns if t & 2, then swap the axes
  * if t & 4 (image_utils.dihedral).  larva_dihedral_inputs_u8 / _f32: in uint8 [N][H][W][3] / float [N][3][H][W] -> the

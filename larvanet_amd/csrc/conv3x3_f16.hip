@@ -23,6 +23,16 @@
 // Every pixel's sum is the same sequence of MFMAs over the same K order whatever tile, batch position or image height
 // it falls into, so results are bit-identical across tilings, bands and batch sizes.
 //
+// Job launches (conv_jobs_kernel): 1..8 independent single-source convs of one shape in one grid -- the legs of a multi-exit
+// network, which depend on the bodies and not on each other.  A workgroup looks its job up from blockIdx.x and then runs
+// conv_tile, the one tile body the single-job kernels run, so job j is bit for bit the single-job launch of its operands.
+// Block b is tile 8 (b / (8 njobs)) + b % 8 of job (b / 8) % njobs: the job index sits between a group of eight tiles and
+// the groups.  Blocks are dealt to the eight XCDs round-robin (observed, relied on for speed only), so b and b + 8 share an
+// L2: the njobs workgroups that read one tile of the shared base image are 8 apart, on one L2 and dispatched together,
+// while the eight neighbouring tiles of one job, which share halo rows of that job's source, stay next to each other as
+// in the single-job grid.  Sources and weights are per job and gain nothing from either order.  The grid is padded to
+// whole groups; a workgroup whose tile does not exist leaves at once.
+//
 // Overflow: an epilogue that stores fp16 sets *flag = 1 (a plain vector store; every writer stores the same value)
 // when the pre-activation value is not finite, or the stored value is not finite or exceeds 65504 in magnitude.  The
 // pre-activation test catches a NaN that the ReLU would otherwise turn into 0.  The uint8 leg end sets it when the fp32
@@ -69,14 +79,42 @@ struct ConvArgs {
   unsigned char* out_u8;   // uint8 [N][4H][4W][3]          (EPI_SHUFFLE_U8)
 };
 
+constexpr int kMaxJobs = 8;
+
+struct JobArgs {
+  const uint16_t* src[kMaxJobs];
+  const uint16_t* wpk[kMaxJobs];
+  const float* bias[kMaxJobs];
+  void* out[kMaxJobs];     // fp16 [N][H][W][48] (EPI_BIAS, EPI_RELU), fp32 [N][3][4H][4W] (EPI_SHUFFLE), uint8 [N][4H][4W][3]
+  const float* base;       // fp32 [N][3][4H][4W], shared by every job
+  unsigned* flag;
+  int njobs, H, W, tiles_x, tiles_y, tiles;   // tiles = N tiles_y tiles_x of ONE job
+};
+
+// One job of a JobArgs as conv_tile reads it: ConvArgs' member names, one source.
+struct JobView {
+  const uint16_t* src[1];
+  static constexpr int nsrc = 1;
+  const uint16_t* wpk;
+  const float* bias;
+  static constexpr const uint16_t* res0 = nullptr;
+  static constexpr const uint16_t* res1 = nullptr;
+  uint16_t* out;
+  const float* base;
+  float* out_hr;
+  unsigned* flag;
+  int H, W, tiles_x, tiles_y;
+  unsigned char* out_u8;
+};
+
 __device__ __forceinline__ h8 as_h8(uint4 v) { return __builtin_bit_cast(h8, v); }
 
-template <int EPI>
-__global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
+// One output tile: tile t of the N x tiles_y x tiles_x tiles of the conv `a` describes (a ConvArgs, or one job's JobView).
+template <int EPI, class Args>
+__device__ __forceinline__ void conv_tile(const Args& a, int t) {
   __shared__ uint4 halo[kHaloSlots];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int hq = lane >> 4, col = lane & 15;
-  int t = blockIdx.x;
   const int tx = t % a.tiles_x;
   t /= a.tiles_x;
   const int ty = t % a.tiles_y;
@@ -190,6 +228,35 @@ __global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
   if (bad) *a.flag = 1u;
 }
 
+template <int EPI>
+__global__ __launch_bounds__(256, 2) void conv_kernel(ConvArgs a) {
+  conv_tile<EPI>(a, (int)blockIdx.x);
+}
+
+// 1..8 single-source convs of one shape in one grid (see the header comment for the block order).  The job and the tile
+// are uniform over the workgroup, so the job's pointers are scalar loads from the kernel arguments.
+template <int EPI>
+__global__ __launch_bounds__(256, 2) void conv_jobs_kernel(JobArgs a) {
+  const unsigned b = blockIdx.x, group = b / (8u * (unsigned)a.njobs);
+  const int job = (int)((b >> 3) - group * (unsigned)a.njobs);
+  const int t = (int)(group * 8u + (b & 7u));
+  if (t >= a.tiles) return;   // (the padding of the last group of eight)
+  JobView v = {};
+  v.src[0] = a.src[job];
+  v.wpk = a.wpk[job];
+  v.bias = a.bias[job];
+  v.base = a.base;
+  v.flag = a.flag;
+  v.H = a.H;
+  v.W = a.W;
+  v.tiles_x = a.tiles_x;
+  v.tiles_y = a.tiles_y;
+  if constexpr (EPI == EPI_SHUFFLE) v.out_hr = static_cast<float*>(a.out[job]);
+  else if constexpr (EPI == EPI_SHUFFLE_U8) v.out_u8 = static_cast<unsigned char*>(a.out[job]);
+  else v.out = static_cast<uint16_t*>(a.out[job]);
+  conv_tile<EPI>(v, t);
+}
+
 // Head: fp32 NCHW image (3 channels) -> fp16 [N][H][W][48], + bias.  fp32 VALU form: fp32 operands (the image and the
 // fp32 weights, not rounded to fp16), fp32 fmaf chain over k = (cin, ky, kx) in PyTorch's weight order, + bias, then
 // one rounding to fp16.  One thread per (pixel, 16-output group); blockIdx.y is the group, so the weights are
@@ -253,9 +320,14 @@ __global__ __launch_bounds__(256) void pack_kernel(const float* __restrict__ w, 
   reinterpret_cast<h8*>(out)[i] = v;
 }
 
-static bool shape_ok(int N, int H, int W) {
+static long long tiles_of(int N, int H, int W) {
+  return (long long)N * ((H + kRows - 1) / kRows) * ((W + kCols - 1) / kCols);
+}
+
+// njobs > 1: the grid of a job launch, njobs times the tiles rounded up to whole groups of eight, must fit as well
+static bool shape_ok(int N, int H, int W, int njobs = 1) {
   return N > 0 && H > 0 && W > 0 && (long long)N * H * W * kC < (1ll << 40) &&
-         (long long)N * ((H + kRows - 1) / kRows) * ((W + kCols - 1) / kCols) < (1ll << 31);
+         (tiles_of(N, H, W) + 7) / 8 * 8 * njobs < (1ll << 31);
 }
 
 static int launch_conv(int epi, ConvArgs& a, int N, hipStream_t s) {
@@ -269,6 +341,39 @@ static int launch_conv(int epi, ConvArgs& a, int N, hipStream_t s) {
     case EPI_RES01: hipLaunchKernelGGL(conv_kernel<EPI_RES01>, grid, block, 0, s, a); break;
     case EPI_SHUFFLE_U8: hipLaunchKernelGGL(conv_kernel<EPI_SHUFFLE_U8>, grid, block, 0, s, a); break;
     default: hipLaunchKernelGGL(conv_kernel<EPI_SHUFFLE>, grid, block, 0, s, a); break;
+  }
+  return (int)hipGetLastError();
+}
+
+// The common part of the two job entry points: argument checks, then one launch.  outs are the njobs output images of
+// the epilogue `epi`; base and flag may be NULL where the epilogue does not use them (the callers have checked).
+static int launch_jobs(int epi, int njobs, const uint16_t* const* srcs, const uint16_t* const* wpks,
+                       const float* const* biases, void* const* outs, const float* base, unsigned* flag, int N, int H,
+                       int W, hipStream_t s) {
+  if (njobs < 1 || njobs > kMaxJobs || !srcs || !wpks || !biases || !outs || !shape_ok(N, H, W, njobs))
+    return (int)hipErrorInvalidValue;
+  JobArgs a = {};
+  for (int j = 0; j < njobs; ++j) {
+    if (!srcs[j] || !wpks[j] || !biases[j] || !outs[j]) return (int)hipErrorInvalidValue;
+    a.src[j] = srcs[j];
+    a.wpk[j] = wpks[j];
+    a.bias[j] = biases[j];
+    a.out[j] = outs[j];
+  }
+  a.base = base;
+  a.flag = flag;
+  a.njobs = njobs;
+  a.H = H;
+  a.W = W;
+  a.tiles_x = (W + kCols - 1) / kCols;
+  a.tiles_y = (H + kRows - 1) / kRows;
+  a.tiles = (int)tiles_of(N, H, W);
+  const dim3 grid((unsigned)((tiles_of(N, H, W) + 7) / 8 * 8 * njobs)), block(256);
+  switch (epi) {
+    case EPI_BIAS: hipLaunchKernelGGL(conv_jobs_kernel<EPI_BIAS>, grid, block, 0, s, a); break;
+    case EPI_RELU: hipLaunchKernelGGL(conv_jobs_kernel<EPI_RELU>, grid, block, 0, s, a); break;
+    case EPI_SHUFFLE_U8: hipLaunchKernelGGL(conv_jobs_kernel<EPI_SHUFFLE_U8>, grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL(conv_jobs_kernel<EPI_SHUFFLE>, grid, block, 0, s, a); break;
   }
   return (int)hipGetLastError();
 }
@@ -355,6 +460,24 @@ int larva_f16_conv3x3_shuffle_base_u8(const uint16_t* src, const uint16_t* wpk, 
   a.H = H;
   a.W = W;
   return launch_conv(EPI_SHUFFLE_U8, a, N, (hipStream_t)stream);
+}
+
+int larva_f16_conv3x3_jobs(int njobs, const uint16_t* const* srcs, const uint16_t* const* wpks,
+                           const float* const* biases, int relu, uint16_t* const* outs, unsigned* flag, int N, int H,
+                           int W, void* stream) {
+  if (!flag) return (int)hipErrorInvalidValue;
+  return launch_jobs(relu ? EPI_RELU : EPI_BIAS, njobs, srcs, wpks, biases, reinterpret_cast<void* const*>(outs), nullptr,
+                     flag, N, H, W, (hipStream_t)stream);
+}
+
+int larva_f16_conv3x3_shuffle_base_jobs(int njobs, const uint16_t* const* srcs, const uint16_t* const* wpks,
+                                        const float* const* biases, const float* base, float* const* outs_f32,
+                                        unsigned char* const* outs_u8, unsigned* flag, int N, int H, int W,
+                                        void* stream) {
+  if (!base || (outs_f32 != nullptr) == (outs_u8 != nullptr) || (outs_u8 && !flag)) return (int)hipErrorInvalidValue;
+  return launch_jobs(outs_u8 ? EPI_SHUFFLE_U8 : EPI_SHUFFLE, njobs, srcs, wpks, biases,
+                     outs_u8 ? reinterpret_cast<void* const*>(outs_u8) : reinterpret_cast<void* const*>(outs_f32), base,
+                     flag, N, H, W, (hipStream_t)stream);
 }
 
 }  // extern "C"

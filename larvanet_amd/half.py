@@ -9,7 +9,10 @@ validate_for_train and every grad-enabled call stay on the fp32 path (the plugin
 gradients).
 
 Every fp16-storing launch sets a device flag when a value leaves the fp16 range (or is not finite); the flag is sticky
-until read (take_overflow)."""
+until read (take_overflow).
+
+HalfForward.exits returns every exit's image from one pass over the head and the bodies: the legs, which do not depend on
+each other, go out as two job launches (K.f16_conv3x3_jobs, K.f16_conv3x3_shuffle_base_jobs)."""
 import torch
 
 from . import kernels as K
@@ -48,6 +51,7 @@ class HalfForward:
         self.net = net
         self._packs = {}
         self._flag = None
+        self._all_exits = False   # exits() has run: refresh() keeps every leg on the exit route packed, not only the end
 
     def _convs(self):
         bodies, end = self.net.route()
@@ -55,7 +59,10 @@ class HalfForward:
         for body in self.net.bodies(bodies):
             for blk in body.res_blocks:
                 out += [blk.body[0], blk.body[2]]
-        if end is not None:
+        if self._all_exits:
+            for leg in self.net.exit_route()[1]:
+                out += [leg.recon_block[0], leg.recon_block[2]]
+        elif end is not None:
             out += ([end.merge_conv] if end.merges else []) + [end.recon_block[0], end.recon_block[2]]
         return out
 
@@ -111,6 +118,48 @@ class HalfForward:
             return K.f16_conv3x3_shuffle_base_u8(h, self._wpk(c2), c2.bias.detach(), base, flag)
         return K.f16_conv3x3_shuffle_base(h, self._wpk(c2), c2.bias.detach(), base)
 
+    def _trunk(self, x, bodies, flag):
+        """The head and the first `bodies` bodies -> every body's output."""
+        net = self.net
+        head = net.head.feature_extraction
+        fea = K.f16_head(x, head.weight.detach(), head.bias.detach(), flag)
+        feats = []
+        for body in net.bodies(bodies):
+            fea = self._body(body, fea, flag)
+            feats.append(fea)
+        return feats
+
+    def exits(self, x, u8=False, batched=True):
+        """Every exit of the module's exit route (net.exit_route()) from ONE pass over the head and the bodies: fp32
+        [M][N][3][4H][4W], or with u8 uint8 [M][N][4H][4W][3]; index 0 is the first exit.  Exit i is bit for bit what
+        __call__ returns on a module whose route ends at leg i.  batched: the M first convs are one job launch and the M
+        leg ends against the shared base another (up to 8 legs per launch); False: one leg after the other."""
+        net = self.net
+        bodies, legs = net.exit_route()
+        self._all_exits = True
+        x = x.contiguous()
+        base = net.base(x)
+        flag = self.flag(x.device)
+        feats = self._trunk(x, bodies, flag)
+        M, (N, _, H, W) = len(legs), (int(v) for v in x.shape)
+        if u8:
+            out = torch.empty((M, N, 4 * H, 4 * W, 3), device=x.device, dtype=torch.uint8)
+        else:
+            out = torch.empty((M, N, 3, 4 * H, 4 * W), device=x.device, dtype=torch.float32)
+        if not batched:
+            for i, leg in enumerate(legs):
+                out[i].copy_(self._leg_end(leg.recon_block, feats[i], base, flag, u8))
+            return out
+        for lo in range(0, M, K.F16_MAX_JOBS):
+            part = legs[lo:lo + K.F16_MAX_JOBS]
+            c1 = [leg.recon_block[0] for leg in part]
+            c2 = [leg.recon_block[2] for leg in part]
+            hs = K.f16_conv3x3_jobs(feats[lo:lo + len(part)], [self._wpk(c) for c in c1], [c.bias.detach() for c in c1],
+                                    flag, relu=True)
+            K.f16_conv3x3_shuffle_base_jobs(list(hs), [self._wpk(c) for c in c2], [c.bias.detach() for c in c2], base,
+                                            flag, u8=u8, out=out[lo:lo + len(part)])
+        return out
+
     def __call__(self, x, u8=False):
         """fp32 [N][3][H][W] -> the fp32 [N][3][4H][4W] image, or with u8 its uint8 [N][4H][4W][3] form
         (K.f32_chw_to_u8_hwc of the former, bit for bit)."""
@@ -121,12 +170,6 @@ class HalfForward:
         if end is None:
             return K.f32_chw_to_u8_hwc(base) if u8 else base
         flag = self.flag(x.device)
-        head = net.head.feature_extraction
-        fea = K.f16_head(x, head.weight.detach(), head.bias.detach(), flag)
-        feats = []
-        for body in net.bodies(bodies):
-            fea = self._body(body, fea, flag)
-            feats.append(fea)
-        if end.merges:
-            fea = self._conv(end.merge_conv, feats, flag)
+        feats = self._trunk(x, bodies, flag)
+        fea = self._conv(end.merge_conv, feats, flag) if end.merges else feats[-1]
         return self._leg_end(end.recon_block, fea, base, flag, u8)

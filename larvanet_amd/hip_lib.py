@@ -141,6 +141,11 @@ SIGNATURES = {
     "larva_f16_conv3x3_shuffle_base_u8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p,
                                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                          ctypes.c_int, ctypes.c_void_p]),
+    "larva_f16_conv3x3_jobs": (ctypes.c_int, [ctypes.c_int, _c_pp, _c_pp, _c_pp, ctypes.c_int, _c_pp, ctypes.c_void_p,
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "larva_f16_conv3x3_shuffle_base_jobs": (ctypes.c_int, [ctypes.c_int, _c_pp, _c_pp, _c_pp, _c_float_p, _c_pp, _c_pp,
+                                                           ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                           ctypes.c_void_p]),
     "larva_u8_hwc_to_f32_chw": (ctypes.c_int, [ctypes.c_void_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_void_p]),
     "larva_f32_chw_to_u8_hwc": (ctypes.c_int, [_c_float_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,

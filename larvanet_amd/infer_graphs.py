@@ -3,11 +3,33 @@ Neither touches the GPU: the plugin (models/LarvaNet.py) hands the table the cal
 from typing import NamedTuple
 
 
-class Form(NamedTuple):
-    """uint8 [N][H][W][3] in and out (u8) or float [N][3][H][W]; the x8 self-ensemble or the plain forward.  Decided once
-    at the entry point and passed down as one value."""
+class _FormPair(NamedTuple):
     u8: bool = False
     ensemble: bool = False
+
+
+class Form(_FormPair):
+    """uint8 [N][H][W][3] in and out (u8) or float [N][3][H][W]; the x8 self-ensemble or the plain forward; every exit's
+    image ([M] in front of the batch: exits) or the route's end alone.  Decided once at the entry point and passed down as
+    one value.  As a tuple it stays the pair (u8, ensemble) that callers unpack; `exits` rides along as an attribute and
+    takes part in equality."""
+
+    def __new__(cls, u8=False, ensemble=False, exits=False):
+        self = super().__new__(cls, u8, ensemble)
+        self.exits = bool(exits)
+        return self
+
+    def __eq__(self, other):
+        return tuple(self) == tuple(other) and self.exits == getattr(other, "exits", False)
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash((tuple(self), self.exits))
+
+    def __repr__(self):
+        return "Form(u8=%r, ensemble=%r, exits=%r)" % (self.u8, self.ensemble, self.exits)
 
 
 class GraphTable(dict):

@@ -214,10 +214,11 @@ def conv3x3(srcs, wpk, cout, bias=None, relu=False, mask=None, res0=None, res1=N
     return out
 
 
-def conv3x3_batch(jobs, cout, relu=False, shuffle=False, logical_w=None):
+def conv3x3_batch(jobs, cout, relu=False, shuffle=False, logical_w=None, outs=None):
     """2..4 INDEPENDENT convs of one shape and one fusion in one launch (their workgroups share
     the CUs two by two).  jobs: dicts with srcs (tensor or list), wpk and optionally bias, mask,
-    res0, res1, base -- a fusion operand is given by every job or by none.  Returns the outputs.
+    res0, res1, base -- a fusion operand is given by every job or by none.  Returns the outputs
+    (outs: the caller's tensors, one per job, e.g. slices of one buffer).
     Falls back to one launch per job where the 16-byte staging path does not apply."""
     lib = hip_lib.load()
     if not 2 <= len(jobs) <= 4:
@@ -235,8 +236,11 @@ def conv3x3_batch(jobs, cout, relu=False, shuffle=False, logical_w=None):
     full, hr = (N, cout, H, P), (N, cout // 16, 4 * H, 4 * W)
     names = ("bias", "res0", "res1", "mask", "base")
     used = {k: norm[0].get(k) is not None for k in names}
+    given = None if outs is None else list(outs)
+    if given is not None and len(given) != len(norm):
+        raise RuntimeError("larvanet_amd: one output tensor per batched conv job")
     src_ptrs, cols, outs = [], {k: [] for k in names}, []
-    for j in norm:
+    for n_job, j in enumerate(norm):
         if len(j["srcs"]) != n_src or any((j.get(k) is not None) != used[k] for k in names):
             raise RuntimeError("larvanet_amd: batched conv jobs must share one shape and one fusion")
         src_ptrs += [_chk(t, "src", (N, cps, H, P)) for t in j["srcs"]]
@@ -244,7 +248,11 @@ def conv3x3_batch(jobs, cout, relu=False, shuffle=False, logical_w=None):
         for k, shape in (("bias", (cout,)), ("res0", full), ("res1", full), ("mask", full), ("base", hr)):
             if used[k]:
                 cols[k].append(_chk(j[k], k, shape))
-        outs.append(torch.empty(hr if shuffle else full, device=j["srcs"][0].device, dtype=torch.float32))
+        if given is None:
+            outs.append(torch.empty(hr if shuffle else full, device=j["srcs"][0].device, dtype=torch.float32))
+        else:
+            _chk(given[n_job], "out", hr if shuffle else full)
+            outs.append(given[n_job])
 
     def arr(k):
         return hip_lib.ptr_array(cols[k]) if used[k] else None
@@ -981,6 +989,57 @@ def f16_conv3x3_shuffle_base_u8(src, wpk, bias, base, flag, out=None):
     hip_lib.check(lib.larva_f16_conv3x3_shuffle_base_u8(src.data_ptr(), wpk.data_ptr(), bias.data_ptr(), base.data_ptr(),
                                                         out.data_ptr(), _chk_flag(flag), N, H, W, _stream()),
                   "larva_f16_conv3x3_shuffle_base_u8")
+    return out
+
+
+F16_MAX_JOBS = 8
+
+
+def _chk_f16_jobs(srcs, wpks, biases):
+    """The per-job operands of a job launch -> ((N, H, W), the three pointer arrays)."""
+    if not (1 <= len(srcs) <= F16_MAX_JOBS and len(wpks) == len(srcs) and len(biases) == len(srcs)):
+        raise RuntimeError("larvanet_amd: an fp16 job launch takes 1 to %d jobs, each with a source, a weight image and "
+                           "a bias" % F16_MAX_JOBS)
+    shape = tuple(int(v) for v in srcs[0].shape)
+    ps = [_chk16(s, "srcs[%d]" % j, shape) for j, s in enumerate(srcs)]
+    for w in wpks:
+        _chk_wpk16(w, 1, "48 -> 48")
+    pb = [_chk(b, "biases[%d]" % j, (F16_CHANNELS,)) for j, b in enumerate(biases)]
+    return shape[:3], (hip_lib.ptr_array(ps), hip_lib.ptr_array([w.data_ptr() for w in wpks]), hip_lib.ptr_array(pb))
+
+
+def f16_conv3x3_jobs(srcs, wpks, biases, flag, relu=False, out=None):
+    """len(srcs) (1..8) independent 48 -> 48 convs of one shape in ONE launch: job j = f16_conv3x3(srcs[j], wpks[j],
+    biases[j], relu=relu), bit for bit -> fp16 [njobs][N][H][W][48] (one tensor; out[j] is job j's)."""
+    lib = hip_lib.load()
+    (N, H, W), arrays = _chk_f16_jobs(srcs, wpks, biases)
+    shape = (len(srcs), N, H, W, F16_CHANNELS)
+    if out is None:
+        out = torch.empty(shape, device=srcs[0].device, dtype=torch.float16)
+    _chk_tensor(out, "out", shape, torch.float16)
+    outs = hip_lib.ptr_array([out[j].data_ptr() for j in range(len(srcs))])
+    hip_lib.check(lib.larva_f16_conv3x3_jobs(len(srcs), *arrays, int(bool(relu)), outs, _chk_flag(flag), N, H, W, _stream()),
+                  "larva_f16_conv3x3_jobs")
+    return out
+
+
+def f16_conv3x3_shuffle_base_jobs(srcs, wpks, biases, base, flag=None, u8=False, out=None):
+    """The leg end of every job against one shared base, in ONE launch: job j = f16_conv3x3_shuffle_base(srcs[j], wpks[j],
+    biases[j], base) -> fp32 [njobs][N][3][4H][4W], or with u8 f16_conv3x3_shuffle_base_u8(...) -> uint8
+    [njobs][N][4H][4W][3] (needs flag), bit for bit."""
+    lib = hip_lib.load()
+    (N, H, W), arrays = _chk_f16_jobs(srcs, wpks, biases)
+    _chk(base, "base", (N, 3, 4 * H, 4 * W))
+    M = len(srcs)
+    shape, dtype = ((M, N, 4 * H, 4 * W, 3), torch.uint8) if u8 else ((M, N, 3, 4 * H, 4 * W), torch.float32)
+    if out is None:
+        out = torch.empty(shape, device=srcs[0].device, dtype=dtype)
+    _chk_tensor(out, "out", shape, dtype)
+    outs = hip_lib.ptr_array([out[j].data_ptr() for j in range(M)])
+    fl = _chk_flag(flag) if (u8 or flag is not None) else None
+    hip_lib.check(lib.larva_f16_conv3x3_shuffle_base_jobs(M, *arrays, base.data_ptr(), None if u8 else outs,
+                                                          outs if u8 else None, fl, N, H, W, _stream()),
+                  "larva_f16_conv3x3_shuffle_base_jobs")
     return out
 
 

@@ -284,6 +284,58 @@ class LarvaNetModule(nn.Module):
         both walk it."""
         return self.len, getattr(self, "body_%d" % (self.len - 1)).leg
 
+    def exit_route(self):
+        """The all-exit route: (how many bodies run, their legs in order) -- every body on the inference route ends in a
+        leg that makes a full image (LarvaNet: all num_modules of them; --leg=k: the first k).  A route whose end merges
+        every body's output (the V2 tail) has no per-body exits."""
+        bodies, end = self.route()
+        name = type(self).__module__.rsplit(".", 1)[-1]
+        if end is not None and end.merges:
+            raise ValueError("larvanet_amd: %s has no per-body exits: its route ends in a tail that merges every body's "
+                             "output (all-exit inference is for LarvaNet / LarvaLeg)" % name)
+        if not bodies:
+            raise ValueError("larvanet_amd: %s --leg=0 returns the base image alone: there is no exit to list" % name)
+        return bodies, [body.leg for body in self.bodies(bodies)]
+
+    def forward_exits(self, x, batched=True):
+        """Every exit's image from one pass over the head and the bodies -> ONE tensor [M][N][3][sH][sW], index 0 the first
+        exit; exit i is bit for bit forward() of a module whose route ends at leg i.  At x4 with batched the legs, which
+        do not depend on each other, go out as K.conv3x3_batch launches of 2..4 jobs (the first convs with ReLU, then the
+        leg ends with the shuffle epilogue against the shared base); a single leg, x2 / x3 or batched=False run one leg
+        after the other (run_leg).  Grad-free."""
+        bodies, legs = self.exit_route()
+        base = self.base(x)
+        with self.width_scope(x):
+            fea = self.head(x)
+            feas = []
+            for body in self.bodies(bodies):
+                fea = body(fea)
+                feas.append(fea)
+            DualChain.join()
+            M = len(legs)
+            out = torch.empty((M,) + tuple(base.shape), device=base.device, dtype=torch.float32)
+            if not (batched and self.scale == 4 and M > 1):
+                for i, leg in enumerate(legs):
+                    out[i].copy_(leg(feas[i], base))
+                return out
+            for leg in legs:
+                for pc in leg._pcs:
+                    pc.refresh()
+            lw = PaddedWidth.current
+            i = 0
+            while i < M:
+                n = 3 if M - i == 5 else min(4, M - i)   # launches of 2..4 legs (5 left = 3 + 2)
+                c1 = [leg.recon_block[0] for leg in legs[i:i + n]]
+                c2 = [leg.recon_block[2] for leg in legs[i:i + n]]
+                hs = K.conv3x3_batch([{"srcs": feas[i + k].contiguous(), "wpk": legs[i + k]._pcs[0].get()[0][0],
+                                       "bias": c1[k].bias.detach()} for k in range(n)],
+                                     int(c1[0].weight.shape[0]), relu=True, logical_w=lw)
+                K.conv3x3_batch([{"srcs": hs[k], "wpk": legs[i + k]._pcs[1].get()[0][0], "bias": c2[k].bias.detach(),
+                                  "base": base} for k in range(n)],
+                                int(c2[0].weight.shape[0]), shuffle=True, logical_w=lw, outs=[out[i + k] for k in range(n)])
+                i += n
+            return out
+
     def forward(self, x):
         bodies, end = self.route()
         base = self.base(x)
@@ -340,6 +392,9 @@ class LarvaNet(BaseModel):
         # prepare() forgets what was captured for the module it replaces: the training step (a CapturedStep or None) ...
         self._step = None
         self._infer_graphs, self._infer_graphs_u8, self._infer_graphs_se = GraphTable(), GraphTable(), GraphTable()
+        self._infer_graphs_ex = GraphTable()   # the all-exit forwards, float and uint8: a table of their own
+        # all exits: the legs as batched launches (None: wherever they apply) or one after the other (tools/time_exits.py)
+        self.batch_exit_legs = None
         # ... and the step in flight: d loss / d loss, the second half of a split backward, the bucket's split (_step_body)
         self._one = self._late = self._early_lo = None
         self._loss_in_flight = False  # how this step's loss reaches the host early: False, "poll" or "split"
@@ -424,7 +479,7 @@ class LarvaNet(BaseModel):
         # whatever was captured reads the module, the gradient bucket and the optimizer that are replaced below
         self._step = self._one = self._late = self._early_lo = self.grad_bucket = None
         self._loss_in_flight = False
-        for table in (self._infer_graphs, self._infer_graphs_u8, self._infer_graphs_se):
+        for table in (self._infer_graphs, self._infer_graphs_u8, self._infer_graphs_se, self._infer_graphs_ex):
             table.clear()
         margs = copy.copy(self.args)
         margs.scale = self.scale
@@ -826,11 +881,12 @@ class LarvaNet(BaseModel):
         # 339 x 510 image (tools/infer_modes.py, round 5).  The capture pays where the launches are short.  The rule asks
         # about the forward's own batch (the ensemble: 8 N slots of a square image, 4 N otherwise) and also picks the head kernel.
         if not (self.use_hip_graph and x.is_cuda) or is_large_inference((8 if h == w else 4) * n if form.ensemble else n, h, w):
-            return self._forward_nograd(x, *form)
-        table = self._infer_graphs_se if form.ensemble else self._infer_graphs_u8 if form.u8 else self._infer_graphs
+            return self._forward_nograd(x, *form, exits=form.exits)
+        table = (self._infer_graphs_ex if form.exits else self._infer_graphs_se if form.ensemble
+                 else self._infer_graphs_u8 if form.u8 else self._infer_graphs)
         tag = ("u8" if form.u8 else "f32", "se") if form.ensemble else ("u8",) if form.u8 else ()
         return table.forward((tuple(x.shape), self.precision) + tag, x, capture=lambda x: self._capture_infer(x, form),
-                             run=lambda x: self._forward_nograd(x, *form))
+                             run=lambda x: self._forward_nograd(x, *form, exits=form.exits))
 
     def _infer(self, x):
         """self.model(x); without gradients, by _eager_or_graph."""
@@ -857,12 +913,12 @@ class LarvaNet(BaseModel):
             with torch.cuda.stream(side):
                 for _ in range(2):
                     with self._infer_scope():
-                        self._forward_nograd(static_x, *form)
+                        self._forward_nograd(static_x, *form, exits=form.exits)
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
                 with self._infer_scope():
-                    out = self._forward_nograd(static_x, *form)
+                    out = self._forward_nograd(static_x, *form, exits=form.exits)
         except Exception as e:   # an optimisation only
             if self.strict_graph:
                 raise
@@ -908,15 +964,25 @@ class LarvaNet(BaseModel):
                 a, b = run(a).contiguous(), run(b).contiguous()
         return K.dihedral_mean(a, b, u8=u8)
 
-    def _forward_nograd(self, x, u8=False, ensemble=False):
+    def _forward_nograd(self, x, u8=False, ensemble=False, exits=False):
         """The inference forward at the model's precision (no graph).  u8: uint8 [N][H][W][3] -> uint8 [N][sH][sW][3],
         the float forward over the exactly converted image, then round half to even + clamp on the device (at fp16 the
-        leg end's epilogue stores the bytes itself).  ensemble: the x8 self-ensemble of either form."""
+        leg end's epilogue stores the bytes itself).  ensemble: the x8 self-ensemble of either form.  exits: every exit's
+        image, [M] in front of the batch (fp32: one conversion launch over the M N images makes the uint8 form)."""
         if ensemble:
             return self._forward_ensemble(x.contiguous(), u8)
         half = self._half()
         if u8:
             x = K.u8_hwc_to_f32_chw(x)
+        if exits:
+            batched = True if self.batch_exit_legs is None else bool(self.batch_exit_legs)
+            if half is not None:
+                return half.exits(x, u8=u8, batched=batched)
+            out = self.model.forward_exits(x, batched=batched)
+            if not u8:
+                return out
+            m, n = int(out.shape[0]), int(out.shape[1])
+            return K.f32_chw_to_u8_hwc(out.view((m * n,) + tuple(out.shape[2:]))).view(m, n, *out.shape[3:], 3)
         if half is not None:
             return half(x, u8=u8)
         out = self.model(x)
@@ -947,13 +1013,13 @@ class LarvaNet(BaseModel):
         half = self._half()
         return half is not None and half.take_overflow()
 
-    def _infer_checked(self, x, u8=False, ensemble=None):
+    def _infer_checked(self, x, u8=False, ensemble=None, exits=False):
         """test and the image entry points, all under no_grad: an fp16 activation that left the fp16 range is an error,
         not a result.  ensemble None: as --self_ensemble says -- the one place the image entry points' form is decided."""
         half = self._half()
         if half is not None:
             half.clear_overflow()
-        out = self._eager_or_graph(x, Form(u8, self._self_ensemble() if ensemble is None else ensemble))
+        out = self._eager_or_graph(x, Form(u8, self._self_ensemble() if ensemble is None else ensemble, exits))
         if self.fp16_overflowed():
             raise self.overflow_error()
         return out
@@ -1036,6 +1102,74 @@ class LarvaNet(BaseModel):
             out = self._infer_checked(x, u8=True)
             records = torch.stack([K.u8_metrics(out[n], truth[n], shave, channel, ssim) for n in range(out.shape[0])])
         return [K.metrics_from_record(r) for r in records.cpu().numpy()]
+
+    # ------------------------------------------------------------------ every exit's image from one forward pass
+    def _check_exits(self):
+        """Refusals of the all-exit entry points, before any device work: a route without per-body exits (ValueError
+        naming the model) and --self_ensemble, which is not built for all exits."""
+        self.model.exit_route()
+        if self._self_ensemble():
+            raise ValueError("larvanet_amd: --self_ensemble together with all-exit inference is not supported; run "
+                             "one of the two")
+
+    def upscale_exits(self, input_list, scale):
+        """upscale() for every exit of the route: list of CHW numpy images -> (M, N, 3, sH, sW) float32 numpy, index 0
+        the first exit.  Exit i is bit for bit upscale() of a LarvaLeg --leg=i+1 plugin with these weights; the head and
+        the bodies run once."""
+        self._check_exits()
+        if int(scale) != self.scale:
+            raise ValueError("larvanet_amd: this model upscales by %d, not by %r" % (self.scale, scale))
+        with torch.no_grad():
+            return self._infer_checked(self._to_input_tensor(input_list), ensemble=False, exits=True).detach().cpu().numpy()
+
+    def upscale_exits_tensor(self, input_list):
+        """upscale_exits() without the trip to the host: (M, N, 3, sH, sW) float32 on self.device."""
+        self._check_exits()
+        with torch.no_grad():
+            return self._infer_checked(self._to_input_tensor(input_list), ensemble=False, exits=True).detach().clone()
+
+    def upscale_exits_u8(self, input_list, scale):
+        """upscale_u8() for every exit: list of uint8 (H, W, 3) images of one shape -> uint8 (M, N, sH, sW, 3) numpy."""
+        self._check_exits()
+        batch = self._check_u8_images(input_list, scale)
+        with torch.no_grad():
+            x = torch.from_numpy(batch).to(self.device)
+            _require_hip(x)
+            return self._infer_checked(x, u8=True, ensemble=False, exits=True).cpu().numpy()
+
+    def upscale_exits_u8_tensor(self, x_u8):
+        """upscale_exits_u8 on the device: uint8 [N][H][W][3] -> uint8 [M][N][sH][sW][3]."""
+        self._check_exits()
+        x = self._check_u8_tensor(x_u8, "upscale_exits_u8_tensor")
+        with torch.no_grad():
+            return self._infer_checked(x, u8=True, ensemble=False, exits=True).clone()
+
+    def evaluate_exits_u8_tensor(self, x_u8, truth_u8, shave=None, channel="y", ssim=True, return_images=False):
+        """evaluate_u8_tensor() for every exit: per image a list of M {"psnr", "ssim", "sse", "n"} dicts, index 0 the
+        first exit (kernels.u8_metrics per exit and image on what upscale_exits_u8_tensor returns).  return_images: ->
+        (that list, the scored uint8 [M][N][sH][sW][3] images on the device)."""
+        self._check_exits()
+        x = self._check_u8_tensor(x_u8, "evaluate_exits_u8_tensor", on_device=False)
+        truth = self._check_u8_tensor(truth_u8, "evaluate_exits_u8_tensor", on_device=False)
+        if truth.shape[0] != x.shape[0]:
+            raise ValueError("larvanet_amd: evaluate_exits_u8_tensor takes as many truth images as inputs, got %d and %d"
+                             % (truth.shape[0], x.shape[0]))
+        if channel not in K.METRIC_CHANNELS:
+            raise ValueError("larvanet_amd: channel must be 'y' or 'rgb', got %r" % (channel,))
+        shave = self.scale if shave is None else int(shave)
+        s = self.scale
+        K.metric_window((s * x.shape[1], s * x.shape[2]), truth.shape[1:3], shave, ssim)   # refusals before any launch
+        _require_hip(x)
+        _require_hip(truth)
+        with torch.no_grad():
+            out = self._infer_checked(x, u8=True, ensemble=False, exits=True)
+            m_exits, n_images = int(out.shape[0]), int(out.shape[1])
+            records = torch.stack([K.u8_metrics(out[i][n], truth[n], shave, channel, ssim)
+                                   for n in range(n_images) for i in range(m_exits)])
+            images = out.clone() if return_images else None
+        recs = records.cpu().numpy()
+        results = [[K.metrics_from_record(recs[n * m_exits + i]) for i in range(m_exits)] for n in range(n_images)]
+        return (results, images) if return_images else results
 
     def receptive_halo(self):
         """LR pixels beyond an output pixel's own LR pixel that can influence it: one per 3x3

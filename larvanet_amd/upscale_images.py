@@ -3,7 +3,11 @@ is written as <output_path>/<stem>.png.
 
     python -m larvanet_amd.upscale_images --model=LarvaNet --num_modules=4 --num_blocks=4,4,4,4 \\
         --restore_path=model.pth --input_path=LR --output_path=SR [--precision fp16] [--self_ensemble]
-        [--io_threads 8]
+        [--io_threads 8] [--all_exits]
+
+--all_exits writes every exit of the multi-exit network from ONE forward pass per image, as <stem>_exit<k>.png with k
+counted from 1 like --leg (model.upscale_exits_u8): the head and the bodies run once, the legs go out together.  It runs
+image by image, outside the stream below.
 
 --self_ensemble (a model flag, like --precision) writes the geometric self-ensemble: the mean of the eight flips /
 transposes of each image run through the network and mapped back, merged on the device.
@@ -38,6 +42,9 @@ def build_parser():
     p.add_argument("--io_threads", type=int, default=None,
                    help="PNG decode / encode threads; default and upper limit: this rank's share of the host's cores")
     p.add_argument("--depth", type=int, default=2, help="images in flight on the device (1 = no copy overlap)")
+    p.add_argument("--all_exits", action="store_true",
+                   help="write every exit's image from one forward pass per image, as <stem>_exit<k>.png (k from 1, like "
+                        "--leg); runs image by image, not through the copy-overlapped stream; LarvaNet / LarvaLeg only")
     return p
 
 
@@ -52,6 +59,11 @@ def shard(files, rank, world):
 
 def output_name(image_name):
     return os.path.splitext(image_name)[0] + ".png"
+
+
+def exit_output_name(image_name, exit_index):
+    """<stem>_exit<k>.png for the 0-based exit_index: k counts from 1, like --leg."""
+    return "%s_exit%d.png" % (os.path.splitext(image_name)[0], exit_index + 1)
 
 
 def io_threads(requested):
@@ -111,10 +123,30 @@ def main(argv=None):
         model.restore(ckpt_path=args.restore_path, target=args.restore_target)
         print("restored the model")
 
+    if args.all_exits:
+        model._check_exits()   # (a model without per-body exits or --self_ensemble: refused before any image is read)
     print("begin super-resolution")
     threads = io_threads(args.io_threads)
     durations = {}
     writes = collections.deque()
+    if args.all_exits:
+        with concurrent.futures.ThreadPoolExecutor(max_workers=threads) as pool:
+            decoded = _prefetched(pool, read_rgb, [os.path.join(args.input_path, n) for n in mine], ahead=threads + 1)
+            last = time.perf_counter()
+            for i, image in enumerate(decoded):
+                outs = model.upscale_exits_u8([image], args.scale)
+                durations[mine[i]] = time.perf_counter() - last
+                for k in range(outs.shape[0]):
+                    writes.append(pool.submit(write_rgb, outs[k, 0], os.path.join(args.output_path, exit_output_name(mine[i], k))))
+                while len(writes) > threads:
+                    writes.popleft().result()
+                print("%d/%d, %s, %d exits, duration: %.4fs" % (i + 1, len(mine), mine[i], outs.shape[0], durations[mine[i]]))
+                last = time.perf_counter()
+            for w in writes:
+                w.result()
+        print("finished")
+        print("- average duration: %.4fs" % np.mean(list(durations.values())))
+        return durations
     with concurrent.futures.ThreadPoolExecutor(max_workers=threads) as pool:
         decoded = _prefetched(pool, read_rgb, [os.path.join(args.input_path, n) for n in mine], ahead=threads + args.depth)
         last = time.perf_counter()
