@@ -452,6 +452,31 @@ int larva_bicubic_down_u8_table(const unsigned char* data, const long long* offs
                                 int planar, unsigned char* out, const long long* out_offsets, const int* tile_prefix,
                                 int total_tiles, void* stream);
 
+/* ---- planar YUV 4:2:0 video frames (csrc/larva_yuv.hip) -----------------------------------------------
+ * An I420 frame of W x H luma pixels is one buffer: Y [H][W], then U [ch][cw], then V [ch][cw], cw = (W + 1) / 2,
+ * ch = (H + 1) / 2 (odd W, H are legal); frame n of a batch of N frames of one size starts at n * frame_pitch_bytes
+ * (>= the frame's bytes).  Chroma is centred on 128 and sited in the centre of its 2 x 2 luma block; a coordinate outside a
+ * plane is clamped to the edge.  Both conversions are exact int32 arithmetic, defined by image_utils.i420_to_rgb_f32 /
+ * rgb_u8_to_i420 and equal to them bit for bit; the matrix (BT.601 / BT.709) and the range (limited / full) are in
+ * coef_table, a HOST array read during the call (image_utils.yuv_to_rgb_table / rgb_to_yuv_table build it).
+ *
+ * larva_i420_to_rgb_f32: coef_table = int[6] {luma offset, cy, crv, cgu, cgv, cbu}, the inverse-matrix entries * 4096.
+ * out fp32 [N][3][H][W], values on [0, 255] in steps of 1 / 256: with u, v = the chroma planes filtered to the luma grid
+ * (9 3 3 1 towards the nearer neighbours, * 16, - 2048) and L = (Y - offset) 16 cy, R = L + crv v, G = L + cgu u + cgv v,
+ * B = L + cbu u, value = clamp((sum + 128) >> 8, 0, 65280) / 256.
+ *
+ * larva_rgb_u8_to_i420: img uint8 [N][H][W][3] -> N frames.  coef_table = int[10] {luma offset, Y row, U row, V row}, the
+ * forward-matrix rows * 65536 (|row| sums <= 2 * 65536): Y = clamp((row . rgb + (offset << 16) + 2^15) >> 16, 0, 255); a
+ * chroma sample, S the per-channel sums of its 2 x 2 block with edge pixels repeated, = clamp((row . S + (128 << 18) +
+ * 2^17) >> 18, 0, 255).  Bytes of a frame's pitch beyond the frame are not touched.
+ *
+ * One launch each, any N, H, W >= 1 (H, W <= 32768); hipErrorInvalidValue before the launch for a NULL pointer, a bad
+ * shape, a pitch below the frame size or a table outside the bounds that keep the sums inside int32. */
+int larva_i420_to_rgb_f32(const unsigned char* frames, long long frame_pitch_bytes, float* out, int N, int H, int W,
+                          const int* coef_table, void* stream);
+int larva_rgb_u8_to_i420(const unsigned char* img, unsigned char* out, long long frame_pitch_bytes, int N, int H, int W,
+                         const int* coef_table, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

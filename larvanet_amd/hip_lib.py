@@ -165,6 +165,10 @@ SIGNATURES = {
     "larva_bicubic_down_u8_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                                    ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                    ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "larva_i420_to_rgb_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, _c_float_p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int, _c_int_p, ctypes.c_void_p]),
+    "larva_rgb_u8_to_i420": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, _c_int_p, ctypes.c_void_p]),
 }
 
 _lib = None

@@ -4,7 +4,8 @@ boundaries.  This is approximate by design (overlap/2 = 10 LR px is less than th
 receptive-field radius of 35) and is reproduced as is.
 
 Also the definitions of the geometric self-ensemble (--self_ensemble): the eight flips / transposes of the square, and
-of the bicubic decimation the low-resolution images of SR benchmarks are made with (bicubic_downscale_u8)."""
+of the bicubic decimation the low-resolution images of SR benchmarks are made with (bicubic_downscale_u8), and of the two
+conversions of the video path between planar YUV 4:2:0 frames and RGB (i420_to_rgb_f32, rgb_u8_to_i420)."""
 import numpy as np
 
 # Bicubic decimation by an integer scale: scale -> (D, first offset, integer numerators).  Output i of an axis takes
@@ -61,6 +62,148 @@ def bicubic_downscale_u8(image, scale):
     q, r = np.floor_divide(a, d2), np.mod(a, d2)                          # floor semantics: 0 <= r < D^2
     q = q + ((2 * r > d2) | ((2 * r == d2) & (q % 2 == 1)))
     return np.clip(q, 0, 255).astype(np.uint8)
+
+
+# ------------------------------------------------------------------ planar YUV 4:2:0 (I420) <-> RGB, in exact integers
+# A frame is ONE contiguous uint8 buffer: Y [H][W], then U [ch][cw], then V [ch][cw], cw = (W + 1) // 2, ch = (H + 1) // 2.
+# Odd W and H are legal; a coordinate outside a plane is the edge's (clamped), reading and writing.  Chroma is centred on
+# 128 and sited in the centre of its 2 x 2 luma block (the JPEG / MPEG-1 position), and only there.  These two functions
+# are the definition; kernels.i420_to_rgb_f32 / rgb_u8_to_i420 (csrc/larva_yuv.hip) equal them bit for bit.
+YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}   # (Kr, Kb); Kg = 1 - Kr - Kb
+YUV_TO_RGB_TABLE_WORDS = 6     # luma offset, cy, crv, cgu, cgv, cbu
+RGB_TO_YUV_TABLE_WORDS = 10    # luma offset, the Y row (R, G, B), the U row, the V row
+
+
+def i420_frame_bytes(width, height):
+    """Bytes of one I420 frame of width x height luma pixels: W H + 2 ((W + 1) // 2) ((H + 1) // 2)."""
+    width, height = int(width), int(height)
+    if width < 1 or height < 1:
+        raise ValueError("larvanet_amd: a frame needs width and height >= 1, got %d x %d" % (width, height))
+    return width * height + 2 * ((width + 1) // 2) * ((height + 1) // 2)
+
+
+def _yuv_params(matrix, full_range):
+    """-> (Kr, Kg, Kb, luma offset, luma span, chroma span)."""
+    if matrix not in YUV_MATRICES:
+        raise ValueError("larvanet_amd: matrix must be one of %s, got %r" % (sorted(YUV_MATRICES), matrix))
+    kr, kb = YUV_MATRICES[matrix]
+    return (kr, 1.0 - kr - kb, kb) + ((0, 255, 255) if full_range else (16, 219, 224))
+
+
+def yuv_to_rgb_matrix(matrix, full_range):
+    """The float64 textbook inverse: R = cy (Y - offset) + crv (V - 128), G = cy (Y - offset) + cgu (U - 128) + cgv (V -
+    128), B = cy (Y - offset) + cbu (U - 128) -> (offset, cy, crv, cgu, cgv, cbu)."""
+    kr, kg, kb, offset, yspan, cspan = _yuv_params(matrix, full_range)
+    c = 255.0 / cspan
+    return (offset, 255.0 / yspan, 2.0 * (1.0 - kr) * c, -2.0 * (1.0 - kb) * kb / kg * c, -2.0 * (1.0 - kr) * kr / kg * c,
+            2.0 * (1.0 - kb) * c)
+
+
+def rgb_to_yuv_matrix(matrix, full_range):
+    """The float64 textbook forward matrix: Y = offset + yr R + yg G + yb B, U = 128 + ur R + ug G + ub B, V likewise ->
+    (offset, (yr, yg, yb), (ur, ug, ub), (vr, vg, vb))."""
+    kr, kg, kb, offset, yspan, cspan = _yuv_params(matrix, full_range)
+    sy, sc = yspan / 255.0, cspan / 255.0
+    u = 0.5 * sc / (1.0 - kb)
+    v = 0.5 * sc / (1.0 - kr)
+    return (offset, (sy * kr, sy * kg, sy * kb), (-u * kr, -u * kg, u * (1.0 - kb)), (v * (1.0 - kr), -v * kg, -v * kb))
+
+
+def yuv_to_rgb_table(matrix, full_range):
+    """The int32 table of i420_to_rgb_f32 (YUV_TO_RGB_TABLE_WORDS): the luma offset and the inverse-matrix entries times
+    4096.  The four chroma entries are rounded to nearest.  The luma gain is rounded UP: 219 * round(255 / 219 * 4096) is
+    69 / 4096 short of 255, and white (Y = 235) has to come out as 255.0 exactly, which the final clamp then gives; it
+    costs 0.69 / 4096 of gain where rounding to nearest costs 0.31 / 4096 (full range: exactly 4096 either way)."""
+    m = yuv_to_rgb_matrix(matrix, full_range)
+    return [int(m[0]), int(np.ceil(m[1] * 4096.0 - 1e-9))] + [int(np.rint(k * 4096.0)) for k in m[2:]]
+
+
+def rgb_to_yuv_table(matrix, full_range):
+    """The int32 table of rgb_u8_to_i420 (RGB_TO_YUV_TABLE_WORDS): the luma offset and the three rows times 65536, rounded
+    to nearest; then the entry of largest magnitude of a row takes what the row's sum is off by, so that the Y row sums
+    to round(span / 255 * 65536) exactly and the U and V rows to 0 exactly (grey stays grey)."""
+    offset, *rows = rgb_to_yuv_matrix(matrix, full_range)
+    span = _yuv_params(matrix, full_range)[4]
+    table = [int(offset)]
+    for row, want in zip(rows, (int(np.rint(span / 255.0 * 65536.0)), 0, 0)):
+        q = [int(np.rint(k * 65536.0)) for k in row]
+        q[int(np.argmax(np.abs(row)))] += want - sum(q)
+        table += q
+    return table
+
+
+def _check_frame(frame, width, height, who):
+    if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8:
+        raise TypeError("larvanet_amd: %s takes a uint8 numpy frame, got %s"
+                        % (who, getattr(frame, "dtype", type(frame).__name__),))
+    n = i420_frame_bytes(width, height)
+    if frame.ndim != 1 or frame.size != n:
+        raise ValueError("larvanet_amd: an I420 frame of %d x %d is a flat buffer of %d bytes, got shape %s"
+                         % (width, height, n, frame.shape,))
+
+
+def i420_planes(frame, width, height):
+    """Views of the Y [H][W], U [ch][cw] and V [ch][cw] planes of a flat I420 frame."""
+    _check_frame(frame, width, height, "i420_planes")
+    cw, ch = (width + 1) // 2, (height + 1) // 2
+    y = frame[:width * height].reshape(height, width)
+    u = frame[width * height:width * height + cw * ch].reshape(ch, cw)
+    v = frame[width * height + cw * ch:].reshape(ch, cw)
+    return y, u, v
+
+
+def _chroma16(c, width, height):
+    """The chroma plane c [ch][cw] at every luma pixel, times 16 and less 2048 (= 16 (C - 128)), int32 [H][W]: for luma
+    pixel (2 i + a, 2 j + b), 9 C[i][j] + 3 C[i][j +- 1] + 3 C[i +- 1][j] + C[i +- 1][j +- 1] - 2048, the sign towards the
+    nearer neighbour (a, b = 0: -1; 1: +1), indices clamped: the bilinear filter of centre-sited chroma."""
+    ch, cw = c.shape
+    c = c.astype(np.int32)
+    rows, cols = np.arange(height), np.arange(width)
+    i, j = rows // 2, cols // 2
+    i2 = np.clip(i + 2 * (rows % 2) - 1, 0, ch - 1)
+    j2 = np.clip(j + 2 * (cols % 2) - 1, 0, cw - 1)
+    return (9 * c[i[:, None], j[None, :]] + 3 * c[i[:, None], j2[None, :]] + 3 * c[i2[:, None], j[None, :]]
+            + c[i2[:, None], j2[None, :]] - 2048)
+
+
+def i420_to_rgb_f32(frame, width, height, matrix="bt601", full_range=False):
+    """One I420 frame -> float32 [3][H][W] RGB on [0, 255] in steps of 1 / 256 (exact in fp32): the network sees the frame
+    without an intermediate rounding to bytes.  With the table (offset, cy, crv, cgu, cgv, cbu) of yuv_to_rgb_table,
+    L = (Y - offset) 16 cy and u, v = _chroma16 of the two planes, the int32 sums with 16 fractional bits are
+    R = L + crv v, G = L + cgu u + cgv v, B = L + cbu u, and a value is clamp((N + 128) >> 8, 0, 255 * 256) / 256 (an
+    arithmetic shift)."""
+    y, u, v = i420_planes(frame, width, height)
+    offset, cy, crv, cgu, cgv, cbu = (np.int32(t) for t in yuv_to_rgb_table(matrix, full_range))
+    lum = (y.astype(np.int32) - offset) * (np.int32(16) * cy)
+    u16, v16 = _chroma16(u, width, height), _chroma16(v, width, height)
+    n = np.stack([lum + crv * v16, lum + cgu * u16 + cgv * v16, lum + cbu * u16])
+    assert n.dtype == np.int32
+    return np.clip((n + 128) >> 8, 0, 255 * 256).astype(np.float32) * np.float32(1.0 / 256.0)
+
+
+def rgb_u8_to_i420(image, matrix="bt601", full_range=False):
+    """uint8 (H, W, 3) RGB -> the flat I420 frame.  With the table (offset, Y row, U row, V row) of rgb_to_yuv_table, all
+    in int32: Y = clamp((sum c v + (offset << 16) + 2^15) >> 16, 0, 255) per pixel, and per chroma sample, S the
+    per-channel sums of its 2 x 2 luma block with the edge pixels repeated, C = clamp((sum c S + (128 << 18) + 2^17) >> 18,
+    0, 255): the block's mean and the matrix in one rounding."""
+    if not isinstance(image, np.ndarray) or image.dtype != np.uint8:
+        raise TypeError("larvanet_amd: rgb_u8_to_i420 takes a uint8 numpy array, got %s"
+                        % (getattr(image, "dtype", type(image).__name__),))
+    if image.ndim != 3 or image.shape[2] != 3 or image.shape[0] < 1 or image.shape[1] < 1:
+        raise ValueError("larvanet_amd: rgb_u8_to_i420 takes an (H, W, 3) image, got shape %s" % (image.shape,))
+    t = [np.int32(k) for k in rgb_to_yuv_table(matrix, full_range)]
+    height, width = image.shape[:2]
+    a = image.astype(np.int32)
+    y = (a[..., 0] * t[1] + a[..., 1] * t[2] + a[..., 2] * t[3] + (t[0] << 16) + (1 << 15)) >> 16
+    r0, c0 = np.arange(0, height, 2), np.arange(0, width, 2)
+    r1, c1 = np.minimum(r0 + 1, height - 1), np.minimum(c0 + 1, width - 1)
+    s = a[r0][:, c0] + a[r0][:, c1] + a[r1][:, c0] + a[r1][:, c1]
+    planes = [np.clip(y, 0, 255)]
+    for k in (4, 7):
+        c = (s[..., 0] * t[k] + s[..., 1] * t[k + 1] + s[..., 2] * t[k + 2] + (128 << 18) + (1 << 17)) >> 18
+        planes.append(np.clip(c, 0, 255))
+    assert all(p.dtype == np.int32 for p in planes)
+    return np.concatenate([p.astype(np.uint8).reshape(-1) for p in planes])
 
 
 def dihedral(a, t, axes=(0, 1)):

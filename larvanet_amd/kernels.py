@@ -1308,3 +1308,66 @@ def bicubic_down_u8_table(data, offsets, hw, scale, out, out_offsets, planar=Fal
                                                   int(bool(planar)), out.data_ptr(), out_offsets.data_ptr(), tiles.data_ptr(),
                                                   int(prefix[n]), _stream()), "larva_bicubic_down_u8_table")
     return out
+
+
+# ------------------------------------------------------------------ planar YUV 4:2:0 frames (csrc/larva_yuv.hip)
+def _chk_frames(t, name, width, height):
+    """A batch of I420 frames: uint8 [N][pitch] on the device, rows contiguous, pitch >= the frame's bytes -> (N, pitch)."""
+    from .image_utils import i420_frame_bytes
+    need = i420_frame_bytes(width, height)
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("larvanet_amd: %s must be a tensor on a HIP device (no CPU path exists)" % name)
+    if t.dtype != torch.uint8:
+        raise RuntimeError("larvanet_amd: %s must be uint8, got %s" % (name, t.dtype))
+    if t.dim() != 2 or int(t.shape[0]) < 1 or int(t.shape[1]) < need:
+        raise RuntimeError("larvanet_amd: %s must be [N][>= %d bytes] (I420 frames of %d x %d), got %s"
+                           % (name, need, width, height, tuple(t.shape)))
+    if t.stride(1) != 1 or (int(t.shape[0]) > 1 and t.stride(0) < need):
+        raise RuntimeError("larvanet_amd: the frames of %s must be contiguous and must not overlap" % name)
+    return int(t.shape[0]), (int(t.stride(0)) if int(t.shape[0]) > 1 else int(t.shape[1]))
+
+
+def _yuv_dims(width, height):
+    width, height = int(width), int(height)
+    if not (1 <= width <= 32768 and 1 <= height <= 32768):
+        raise RuntimeError("larvanet_amd: a frame's width and height must be 1 .. 32768, got %d x %d" % (width, height))
+    return width, height
+
+
+def i420_to_rgb_f32(frames, width, height, matrix="bt601", full_range=False, out=None):
+    """uint8 [N][pitch] I420 frames of width x height (pitch >= image_utils.i420_frame_bytes) -> float32 [N][3][H][W] RGB
+    on [0, 255] in steps of 1 / 256: image_utils.i420_to_rgb_f32 per frame, bit for bit, in one launch."""
+    from .image_utils import yuv_to_rgb_table
+    lib = hip_lib.load()
+    W, H = _yuv_dims(width, height)
+    table = hip_lib.int_array(yuv_to_rgb_table(matrix, full_range))
+    N, pitch = _chk_frames(frames, "frames", W, H)
+    if out is None:
+        out = torch.empty((N, 3, H, W), device=frames.device, dtype=torch.float32)
+    _chk(out, "out", (N, 3, H, W))
+    if out.device != frames.device:
+        raise RuntimeError("larvanet_amd: frames and out must be on one device")
+    hip_lib.check(lib.larva_i420_to_rgb_f32(frames.data_ptr(), pitch, out.data_ptr(), N, H, W, table, _stream()),
+                  "larva_i420_to_rgb_f32")
+    return out
+
+
+def rgb_u8_to_i420(x, matrix="bt601", full_range=False, out=None):
+    """uint8 [N][H][W][3] RGB -> uint8 [N][frame bytes] I420 frames: image_utils.rgb_u8_to_i420 per image, bit for bit, in
+    one launch.  out: uint8 [N][pitch >= frame bytes] to fill (bytes of a row beyond the frame are left alone)."""
+    from .image_utils import i420_frame_bytes, rgb_to_yuv_table
+    lib = hip_lib.load()
+    table = hip_lib.int_array(rgb_to_yuv_table(matrix, full_range))
+    _chk_u8(x, "x")
+    N, H, W = (int(v) for v in x.shape[:3])
+    if N < 1:
+        raise RuntimeError("larvanet_amd: x must not be empty, got %s" % (tuple(x.shape),))
+    _yuv_dims(W, H)
+    if out is None:
+        out = torch.empty((N, i420_frame_bytes(W, H)), device=x.device, dtype=torch.uint8)
+    n_out, pitch = _chk_frames(out, "out", W, H)
+    if n_out != N or out.device != x.device:
+        raise RuntimeError("larvanet_amd: out must hold %d frames on x's device, got %s" % (N, tuple(out.shape)))
+    hip_lib.check(lib.larva_rgb_u8_to_i420(x.data_ptr(), out.data_ptr(), pitch, N, H, W, table, _stream()),
+                  "larva_rgb_u8_to_i420")
+    return out

@@ -26,6 +26,7 @@ from ..autograd import step_prologue as autograd_step_prologue
 from ..captured_step import CapturedStep, LossCopy
 from ..infer_graphs import Form, GraphTable
 from ..optim import FlatAdamW, flatten_parameters
+from ..image_utils import YUV_MATRICES, i420_frame_bytes
 from ..metrics import image_psnr, image_to_uint8, fit_truth_image_size
 from .base import BaseModel
 
@@ -875,7 +876,8 @@ class LarvaNet(BaseModel):
         its own limit, so each path captures exactly what it would without the others).  A replay returns the graph's
         output buffer: callers that keep it across calls copy it."""
         n = int(x.shape[0])
-        h, w = (int(v) for v in (x.shape[1:3] if form.u8 else x.shape[2:4]))
+        hwc = form.u8 and x.dtype == torch.uint8   # (the video path's u8 form takes float planes: _infer_checked)
+        h, w = (int(v) for v in (x.shape[1:3] if hwc else x.shape[2:4]))
         # A whole validation image is 36 launches of 60 us each: the host is ~2 ms ahead of the GPU after the first few,
         # and eager launches have no replay boundary and no copy into a static input: 2.162 against 2.178 ms per
         # 339 x 510 image (tools/infer_modes.py, round 5).  The capture pays where the launches are short.  The rule asks
@@ -885,6 +887,8 @@ class LarvaNet(BaseModel):
         table = (self._infer_graphs_ex if form.exits else self._infer_graphs_se if form.ensemble
                  else self._infer_graphs_u8 if form.u8 else self._infer_graphs)
         tag = ("u8" if form.u8 else "f32", "se") if form.ensemble else ("u8",) if form.u8 else ()
+        if form.u8 and not hwc:
+            tag += ("f32in",)
         return table.forward((tuple(x.shape), self.precision) + tag, x, capture=lambda x: self._capture_infer(x, form),
                              run=lambda x: self._forward_nograd(x, *form, exits=form.exits))
 
@@ -901,7 +905,8 @@ class LarvaNet(BaseModel):
         return self._eager_or_graph(x, Form(u8, True))
 
     def _infer_u8_images(self, x_u8):
-        """What the streams (pipeline.py) run on a uint8 device batch: _infer_u8, or under --self_ensemble the ensemble."""
+        """What the streams (pipeline.py) run on a uint8 device batch: _infer_u8, or under --self_ensemble the ensemble.
+        The video stream hands it the float planes of its frames instead (see _forward_nograd)."""
         return self._eager_or_graph(x_u8, Form(True, self._self_ensemble()))
 
     def _capture_infer(self, x, form):
@@ -950,7 +955,7 @@ class LarvaNet(BaseModel):
         on its batch slot, so this is the composition of eight plain calls bit for bit; the head kernel, whose two forms
         do differ, is chosen as the plain call of these N images would choose it."""
         n = int(x.shape[0])
-        h, w = (int(v) for v in (x.shape[1:3] if u8 else x.shape[2:4]))
+        h, w = (int(v) for v in (x.shape[1:3] if x.dtype == torch.uint8 else x.shape[2:4]))
         half = self._half()
         run = half if half is not None else self.model
         with HeadFn.rule_batch_as(n):
@@ -967,12 +972,13 @@ class LarvaNet(BaseModel):
     def _forward_nograd(self, x, u8=False, ensemble=False, exits=False):
         """The inference forward at the model's precision (no graph).  u8: uint8 [N][H][W][3] -> uint8 [N][sH][sW][3],
         the float forward over the exactly converted image, then round half to even + clamp on the device (at fp16 the
-        leg end's epilogue stores the bytes itself).  ensemble: the x8 self-ensemble of either form.  exits: every exit's
+        leg end's epilogue stores the bytes itself); a float32 [N][3][H][W] input (the video path: frames converted
+        without a rounding to bytes) is taken as it is and leaves as uint8 the same way.  ensemble: the x8 self-ensemble of either form.  exits: every exit's
         image, [M] in front of the batch (fp32: one conversion launch over the M N images makes the uint8 form)."""
         if ensemble:
             return self._forward_ensemble(x.contiguous(), u8)
         half = self._half()
-        if u8:
+        if u8 and x.dtype == torch.uint8:
             x = K.u8_hwc_to_f32_chw(x)
         if exits:
             batched = True if self.batch_exit_legs is None else bool(self.batch_exit_legs)
@@ -1102,6 +1108,52 @@ class LarvaNet(BaseModel):
             out = self._infer_checked(x, u8=True)
             records = torch.stack([K.u8_metrics(out[n], truth[n], shave, channel, ssim) for n in range(out.shape[0])])
         return [K.metrics_from_record(r) for r in records.cpu().numpy()]
+
+    # ------------------------------------------------------------------ video: planar YUV 4:2:0 frames in and out
+    def _check_yuv_args(self, width, height, matrix, full_range, scale=None):
+        """Host-side checks shared by the video entry points (before any device work) -> (W, H, LR frame bytes)."""
+        if scale is not None and int(scale) != self.scale:
+            raise ValueError("larvanet_amd: this model upscales by %d, not by %r" % (self.scale, scale))
+        if matrix not in YUV_MATRICES:
+            raise ValueError("larvanet_amd: matrix must be one of %s, got %r" % (sorted(YUV_MATRICES), matrix))
+        if not isinstance(full_range, (bool, np.bool_)):
+            raise TypeError("larvanet_amd: full_range must be True or False, got %r" % (full_range,))
+        width, height = int(width), int(height)
+        return width, height, i420_frame_bytes(width, height)
+
+    def upscale_yuv420_tensor(self, buf_u8, width, height, matrix="bt601", full_range=False):
+        """uint8 [N][frame bytes] on self.device, N I420 frames of width x height (image_utils.i420_frame_bytes) ->
+        uint8 [N][HR frame bytes], the frames of (s width) x (s height).  Byte for byte
+        rgb_u8_to_i420(f32_chw_to_u8_hwc(forward(i420_to_rgb_f32(frame)))) of image_utils, forward the inference at this
+        model's precision (fp16 overflow raises FloatingPointError; --self_ensemble is honoured)."""
+        width, height, nbytes = self._check_yuv_args(width, height, matrix, full_range)
+        if not isinstance(buf_u8, torch.Tensor) or buf_u8.dtype != torch.uint8:
+            raise TypeError("larvanet_amd: upscale_yuv420_tensor takes a uint8 tensor, got %s"
+                            % (getattr(buf_u8, "dtype", type(buf_u8).__name__),))
+        if buf_u8.dim() != 2 or buf_u8.shape[0] < 1 or buf_u8.shape[1] != nbytes:
+            raise ValueError("larvanet_amd: upscale_yuv420_tensor takes [N][%d] (I420 frames of %d x %d), got shape %s"
+                             % (nbytes, width, height, tuple(buf_u8.shape)))
+        _require_hip(buf_u8)
+        with torch.no_grad():   # (the two conversions are launches of their own, outside the forward's cached graph)
+            x = K.i420_to_rgb_f32(buf_u8.contiguous(), width, height, matrix, bool(full_range))
+            return K.rgb_u8_to_i420(self._infer_checked(x, u8=True), matrix, bool(full_range))
+
+    def upscale_yuv420(self, frames, scale, width, height, matrix="bt601", full_range=False):
+        """list of uint8 1-D numpy I420 frames of width x height -> list of the uint8 1-D HR frames of (s width) x
+        (s height): upscale_yuv420_tensor with the trips over the host link, 1.5 bytes per pixel each way."""
+        width, height, nbytes = self._check_yuv_args(width, height, matrix, full_range, scale)
+        if isinstance(frames, np.ndarray) or not len(frames):
+            raise ValueError("larvanet_amd: upscale_yuv420 takes a non-empty list of 1-D uint8 frames")
+        for f in frames:
+            if not isinstance(f, np.ndarray) or f.dtype != np.uint8:
+                raise TypeError("larvanet_amd: upscale_yuv420 takes uint8 numpy frames, got %s"
+                                % (getattr(f, "dtype", type(f).__name__),))
+            if f.ndim != 1 or f.size != nbytes:
+                raise ValueError("larvanet_amd: an I420 frame of %d x %d is a flat buffer of %d bytes (one size per call), "
+                                 "got shape %s" % (width, height, nbytes, f.shape,))
+        buf = torch.from_numpy(np.ascontiguousarray(np.stack(frames))).to(self.device)
+        _require_hip(buf)
+        return list(self.upscale_yuv420_tensor(buf, width, height, matrix, full_range).cpu().numpy())
 
     # ------------------------------------------------------------------ every exit's image from one forward pass
     def _check_exits(self):

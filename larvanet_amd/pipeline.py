@@ -19,6 +19,10 @@ the input, the metric launch (kernels.u8_metrics) follows the forward on the com
 record comes back unless the images are kept.  A pair whose input is None has it made from the truth on the device
 (kernels.bicubic_down_u8 on the compute stream, between the truth's arrival and the forward): no LR image is read,
 pinned or copied.
+
+upscale_yuv_stream() is the same pipeline over planar YUV 4:2:0 video frames: a frame travels in and out as its 1.5 bytes
+per pixel, and the two colour conversions (kernels.i420_to_rgb_f32 / rgb_u8_to_i420) are two launches on the compute
+stream around the forward, the second one writing straight into the slot's output buffer.
 """
 import collections
 
@@ -136,10 +140,41 @@ def evaluate_stream(model, pairs, scale, shave=None, channel="y", ssim=True, dep
     return _stream(model, pairs, depth, {"shave": shave, "channel": channel, "ssim": bool(ssim), "keep": bool(keep_images)})
 
 
-def _stream(model, images, depth, score=None):
-    """The pipeline of upscale_stream; with `score` (evaluate_stream's settings) the items are (input, truth) pairs."""
-    if score is not None:
+def _check_frame(f, nbytes, width, height):
+    if not isinstance(f, np.ndarray) or f.dtype != np.uint8:
+        raise TypeError("larvanet_amd: upscale_yuv_stream takes uint8 numpy frames, got %s"
+                        % (getattr(f, "dtype", type(f).__name__),))
+    if f.ndim != 1 or f.size != nbytes:
+        raise ValueError("larvanet_amd: an I420 frame of %d x %d is a flat buffer of %d bytes, got shape %s"
+                         % (width, height, nbytes, f.shape,))
+
+
+def upscale_yuv_stream(model, frames, scale, width=None, height=None, matrix="bt601", full_range=False, depth=2):
+    """Generator: uint8 1-D numpy I420 frames of width x height -> their uint8 1-D HR frames of (s width) x (s height), in
+    input order; each equals model.upscale_yuv420([frame], scale, width, height, matrix, full_range)[0].  With width and
+    height None the items are (frame, width, height) triples of any mix of sizes.  upscale_stream's pipeline: pinned
+    staging slots, one copy stream, at most `depth` frames in flight; under --precision fp16 a frame whose activations
+    overflow raises FloatingPointError when its turn to be yielded comes, the frames before it have been yielded."""
+    depth = int(depth)
+    if depth < 1:
+        raise ValueError("larvanet_amd: upscale_yuv_stream needs depth >= 1")
+    if (width is None) != (height is None):
+        raise ValueError("larvanet_amd: upscale_yuv_stream takes width and height, or neither (items are then "
+                         "(frame, width, height) triples)")
+    model._check_yuv_args(1 if width is None else width, 1 if height is None else height, matrix, full_range, scale)
+    if model.device.type != "cuda":
+        raise RuntimeError("larvanet_amd: upscale_yuv_stream only runs on a HIP device (MI355X); there is no CPU fallback")
+    size = None if width is None else (int(width), int(height))
+    return _stream(model, frames, depth, yuv={"size": size, "matrix": matrix, "full_range": bool(full_range)})
+
+
+def _stream(model, images, depth, score=None, yuv=None):
+    """The pipeline of upscale_stream; with `score` (evaluate_stream's settings) the items are (input, truth) pairs; with
+    `yuv` (upscale_yuv_stream's settings) they are I420 frames, or (frame, width, height) triples."""
+    if score is not None or yuv is not None:
         from . import kernels as K
+    if yuv is not None:
+        from .image_utils import i420_frame_bytes
     keep = score is None or score["keep"]
     compute = torch.cuda.current_stream()
     copy = torch.cuda.Stream()
@@ -169,6 +204,8 @@ def _stream(model, images, depth, score=None):
         if fp16 and int(slot.pin_flag[0]):
             raise model.overflow_error()
         out = np.array(slot.views_out(slot.out_shape)[0].numpy()[0]) if keep else None
+        if yuv is not None:
+            out = out[0]   # (the frame itself, 1-D)
         result = None if score is None else K.metrics_from_record(slot.pin_record.numpy().copy())
         free.append(slot)
         if score is None:
@@ -180,7 +217,12 @@ def _stream(model, images, depth, score=None):
             if fp16:
                 model_flag.zero_()
             for image in images:
-                if score is None:
+                if yuv is not None:
+                    image, fw, fh = (image,) + yuv["size"] if yuv["size"] is not None else image
+                    fw, fh = int(fw), int(fh)
+                    _check_frame(image, i420_frame_bytes(fw, fh), fw, fh)
+                    image = image[None]   # (a batch of one frame: [1][frame bytes])
+                elif score is None:
                     _check_image(image)
                 else:
                     image, truth = image
@@ -216,10 +258,16 @@ def _stream(model, images, depth, score=None):
                 compute.wait_event(slot.h2d)
                 if made:
                     K.bicubic_down_u8(dev_truth, model.scale, out=dev_in[0])
-                out = model._infer_u8_images(dev_in)   # (the x8 self-ensemble under --self_ensemble)
-                slot.out_shape = tuple(out.shape)
-                if keep:
-                    slot.views_out(slot.out_shape)[1].copy_(out)
+                if yuv is not None:   # frame -> float planes -> forward -> HR frame, written into the slot's own buffer
+                    x = K.i420_to_rgb_f32(dev_in[0], fw, fh, yuv["matrix"], yuv["full_range"])
+                    out = model._infer_u8_images(x)
+                    slot.out_shape = (1, 1, i420_frame_bytes(model.scale * fw, model.scale * fh))
+                    K.rgb_u8_to_i420(out, yuv["matrix"], yuv["full_range"], out=slot.views_out(slot.out_shape)[1][0])
+                else:
+                    out = model._infer_u8_images(dev_in)   # (the x8 self-ensemble under --self_ensemble)
+                    slot.out_shape = tuple(out.shape)
+                    if keep:
+                        slot.views_out(slot.out_shape)[1].copy_(out)
                 if score is not None:   # (scored where the forward left it: nothing else runs on this stream in between)
                     K.u8_metrics(out[0], dev_truth, score["shave"], score["channel"], score["ssim"],
                                  result=slot.records(K.METRIC_RESULT_WORDS)[1])

@@ -1,0 +1,206 @@
+"""Video upscaler: 8-bit planar YUV 4:2:0 frames in, the upscaled frames out, as a Y4M (YUV4MPEG2) stream or a headerless
+.yuv file; `-` is stdin / stdout, so it sits between two ffmpeg processes (the package never calls ffmpeg itself):
+
+    ffmpeg -i in.mp4 -f yuv4mpegpipe -pix_fmt yuv420p - | \\
+    python -m larvanet_amd.upscale_video --model=LarvaNet --num_modules=4 --num_blocks=4,4,4,4 --restore_path=model.pth \\
+        --input - --output - [--precision fp16] [--self_ensemble] [--matrix bt709] [--range limited|full] | \\
+    ffmpeg -i - out.mp4
+
+    python -m larvanet_amd.upscale_video ... --input in.yuv --width 510 --height 339 --output out.yuv
+
+The frames stay YUV end to end (pipeline.upscale_yuv_stream): 1.5 bytes per pixel cross the host link each way, the two
+colour conversions run on the device, and no pass over a frame happens on the host.  One thread reads frames, one writes
+them; the stream runs between them.  A file whose name ends in .y4m, and stdin / stdout unless --width and --height are
+given, is a Y4M stream: its header gives the size, and XCOLORRANGE=FULL selects full range unless --range is given.  The
+output header carries the upscaled size and the input's F, A, C and X tags.  Only 8-bit 4:2:0 is processed (y4m.py lists
+what is refused), always as centre-sited chroma."""
+import argparse
+import importlib
+import os
+import queue
+import sys
+import threading
+import time
+
+from . import y4m
+from .image_utils import YUV_MATRICES
+
+_END = object()
+
+
+def build_parser():
+    p = argparse.ArgumentParser()
+    p.add_argument("--model", type=str, default="LarvaNet")
+    p.add_argument("--scale", type=int, default=4)
+    p.add_argument("--cuda_device", type=str, default=None)
+    p.add_argument("--restore_path", type=str, default=None,
+                   help="checkpoint (bare state_dict); omitted = freshly initialised weights")
+    p.add_argument("--restore_target", type=str)
+    p.add_argument("--restore_global_step", type=int, default=0)
+    p.add_argument("--input", type=str, required=True, help="a .y4m or .yuv file, or - for stdin")
+    p.add_argument("--output", type=str, required=True, help="a .y4m or .yuv file, or - for stdout")
+    p.add_argument("--matrix", type=str, default="bt601", choices=sorted(YUV_MATRICES))
+    p.add_argument("--range", type=str, default=None, choices=["limited", "full"],
+                   help="default: what the Y4M header's XCOLORRANGE says, else limited")
+    p.add_argument("--width", type=int, default=None, help="frame width of a headerless .yuv input")
+    p.add_argument("--height", type=int, default=None, help="frame height of a headerless .yuv input")
+    p.add_argument("--depth", type=int, default=2, help="frames in flight on the device (1 = no copy overlap)")
+    return p
+
+
+def input_is_y4m(args):
+    """A name ending in .y4m is Y4M, one ending in .yuv is headerless; anything else (stdin) is headerless exactly when
+    --width and --height are given."""
+    name = args.input.lower()
+    if name.endswith(".y4m"):
+        return True
+    if name.endswith(".yuv"):
+        return False
+    return args.width is None and args.height is None
+
+
+def check_args(args):
+    """Refusals that need neither the input nor a device."""
+    if args.depth < 1:
+        raise ValueError("larvanet_amd.upscale_video: --depth must be >= 1")
+    if args.scale not in (2, 3, 4):
+        raise ValueError("larvanet_amd.upscale_video: --scale must be 2, 3 or 4, got %d" % args.scale)
+    if (args.width is None) != (args.height is None):
+        raise ValueError("larvanet_amd.upscale_video: --width and --height go together")
+    if input_is_y4m(args):
+        if args.width is not None:
+            raise ValueError("larvanet_amd.upscale_video: a Y4M input carries its own size; drop --width and --height")
+    else:
+        if args.width is None:
+            raise ValueError("larvanet_amd.upscale_video: a headerless .yuv input needs --width and --height")
+        if args.width < 1 or args.height < 1:
+            raise ValueError("larvanet_amd.upscale_video: --width and --height must be >= 1")
+
+
+def open_input(args, stream=None):
+    """-> (Header or None, (width, height), full_range, frame generator, the stream to close).  Reads the Y4M header:
+    everything this package cannot process is refused here, before any device work."""
+    if stream is None:
+        stream = sys.stdin.buffer if args.input == "-" else open(args.input, "rb")
+    if input_is_y4m(args):
+        header = y4m.read_header(stream)
+        size = (header.width, header.height)
+        frames = y4m.read_frames(stream, header)
+        said = header.full_range
+    else:
+        header, size, said = None, (args.width, args.height), None
+        frames = y4m.read_raw_frames(stream, *size)
+    full = (args.range == "full") if args.range is not None else bool(said)
+    return header, size, full, frames, stream
+
+
+def _reader(frames, q, stop):
+    try:
+        for f in frames:
+            while not stop.is_set():
+                try:
+                    q.put(f, timeout=0.1)
+                    break
+                except queue.Full:
+                    pass
+            if stop.is_set():
+                return
+        q.put(_END)
+    except BaseException as e:   # (a truncated frame: handed to the main thread, which raises it at that frame's turn)
+        q.put(e)
+
+
+def _writer(out, is_y4m, q, failed):
+    f = None
+    try:
+        while True:
+            f = q.get()
+            if f is _END:
+                return
+            if is_y4m:
+                y4m.write_frame(out, f)
+            else:
+                out.write(memoryview(f))
+    except BaseException as e:   # (a closed pipe, a full disk: raised by the main thread)
+        failed.append(e)
+        while f is not _END:   # (keep draining so the main thread never blocks on a full queue)
+            f = q.get()
+
+
+def _queued(q):
+    while True:
+        f = q.get()
+        if f is _END:
+            return
+        if isinstance(f, BaseException):
+            raise f
+        yield f
+
+
+def run(model, args, header, size, full_range, frames, out_raw):
+    """The reader thread, pipeline.upscale_yuv_stream and the writer thread -> the number of frames written."""
+    from . import pipeline
+    if header is not None:
+        y4m.write_header(out_raw, header.scaled(args.scale))
+    q_in, q_out = queue.Queue(maxsize=args.depth + 2), queue.Queue(maxsize=args.depth + 2)
+    stop, failed = threading.Event(), []
+    reader = threading.Thread(target=_reader, args=(frames, q_in, stop), daemon=True)
+    writer = threading.Thread(target=_writer, args=(out_raw, header is not None, q_out, failed), daemon=True)
+    reader.start()
+    writer.start()
+    count = 0
+    try:
+        for hr in pipeline.upscale_yuv_stream(model, _queued(q_in), args.scale, size[0], size[1], matrix=args.matrix,
+                                              full_range=full_range, depth=args.depth):
+            if failed:
+                raise failed[0]
+            q_out.put(hr)
+            count += 1
+    finally:
+        stop.set()
+        q_out.put(_END)
+        writer.join()
+    if failed:
+        raise failed[0]
+    out_raw.flush()
+    return count
+
+
+def main(argv=None):
+    args, remaining = build_parser().parse_known_args(argv)
+    check_args(args)
+    log = sys.stderr   # (stdout may be the video)
+    if args.cuda_device is not None and "LOCAL_RANK" not in os.environ:
+        os.environ["HIP_VISIBLE_DEVICES"] = args.cuda_device
+    header, size, full_range, frames, in_stream = open_input(args)
+    try:
+        if header is not None and header.siting_warning():
+            print(header.siting_warning(), file=log)
+        print("video: %d x %d -> %d x %d, %s, %s range" % (size[0], size[1], size[0] * args.scale, size[1] * args.scale,
+                                                          args.matrix, "full" if full_range else "limited"), file=log)
+        print("prepare model - %s" % args.model, file=log)
+        model = importlib.import_module("larvanet_amd.models." + args.model).create_model()
+        _, remaining = model.parse_args(remaining)
+        model.prepare(is_training=False, scales=[args.scale], global_step=args.restore_global_step)
+        if remaining:
+            print("WARNING: found unhandled arguments: %s" % remaining, file=log)
+        if args.restore_path is not None:
+            model.restore(ckpt_path=args.restore_path, target=args.restore_target)
+            print("restored the model", file=log)
+        out_raw = sys.stdout.buffer if args.output == "-" else open(args.output, "wb")
+        try:
+            t0 = time.perf_counter()
+            count = run(model, args, header, size, full_range, frames, out_raw)
+            dt = time.perf_counter() - t0
+        finally:
+            if args.output != "-":
+                out_raw.close()
+    finally:
+        if args.input != "-":
+            in_stream.close()
+    print("finished: %d frames, %.2f frames per second" % (count, count / dt if dt > 0 else 0.0), file=log)
+    return count
+
+
+if __name__ == "__main__":
+    main()
