@@ -477,6 +477,18 @@ int larva_i420_to_rgb_f32(const unsigned char* frames, long long frame_pitch_byt
 int larva_rgb_u8_to_i420(const unsigned char* img, unsigned char* out, long long frame_pitch_bytes, int N, int H, int W,
                          const int* coef_table, void* stream);
 
+/* ---- bicubic resize of uint8 images to any size (csrc/larva_resize.hip) ----------------------------------
+ * Pillow's Image.resize((w, h), Image.BICUBIC) of an RGB uint8 image, byte for byte, both passes in ONE launch, int32 only.
+ * src uint8 [N][H][W][3] -> dst uint8 [N][h][w][3], both contiguous, H <= 4 h and W <= 4 w (any upsampling).  Per axis two
+ * DEVICE int32 tables (image_utils.resize_coeffs makes them): bounds [n_out][2] = (lo, n) and coeffs [n_out][ksize], ksize =
+ * 2 ceil(2 max(n_in / n_out, 1)) + 1 <= 17; one pass is out[i] = clamp((2^21 + sum_{j < n} in[lo + j] coeffs[i][j]) >> 22, 0,
+ * 255) (arithmetic shift).  The horizontal pass (hbounds, hcoeffs, kx) runs first and leaves bytes, then the vertical one
+ * (vbounds, vcoeffs, ky).  An axis whose size does not change passes ksize 0 and NULL tables and is copied.
+ * hipErrorInvalidValue before the launch for a NULL pointer, a size below 1 or above 2^20, N above 65535, a ratio above 4,
+ * a ksize that is not the one of the axis' ratio, or more than 65535 * 16 output rows. */
+int larva_resize_u8(const unsigned char* src, unsigned char* dst, int N, int H, int W, int h, int w, const int* hbounds,
+                    const int* hcoeffs, int kx, const int* vbounds, const int* vcoeffs, int ky, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -169,6 +169,9 @@ SIGNATURES = {
                                              ctypes.c_int, _c_int_p, ctypes.c_void_p]),
     "larva_rgb_u8_to_i420": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
                                             ctypes.c_int, _c_int_p, ctypes.c_void_p]),
+    "larva_resize_u8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
 }
 
 _lib = None

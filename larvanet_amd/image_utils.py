@@ -64,6 +64,118 @@ def bicubic_downscale_u8(image, scale):
     return np.clip(q, 0, 255).astype(np.uint8)
 
 
+# ------------------------------------------------------------------ bicubic resize to any size: Pillow's, byte for byte
+# Image.resize((w, h), Image.BICUBIC) of an RGB uint8 image restated.  Per axis: scale = n_in / n_out, fs = max(scale, 1),
+# support = 2 fs, ksize = 2 ceil(support) + 1.  Output i has its centre at c = (i + 1/2) scale and takes the inputs lo ..
+# lo + n - 1, lo = max(int(c - support + 1/2), 0), n = min(int(c + support + 1/2), n_in) - lo, with the weights
+# cubic((j + lo - c + 1/2) / fs) (Keys, a = -1/2) summed in index order in float64, divided by their sum and fixed to
+# K_j = int(k_j 2^22 +- 1/2) (away from zero).  One pass is out = clamp((2^21 + sum_j in[lo + j] K_j) >> 22, 0, 255) in
+# int32 with an arithmetic shift; the horizontal pass runs first and leaves BYTES, then the vertical one; an axis whose
+# size does not change is skipped.  kernels.resize_u8 (csrc/larva_resize.hip) equals resize_u8 bit for bit.
+RESIZE_PRECISION_BITS = 22
+RESIZE_MAX_RATIO = 4     # n_in <= 4 n_out per axis (any upsampling), so that ksize <= RESIZE_MAX_TAPS
+RESIZE_MAX_TAPS = 17
+
+
+def check_resize(in_h, in_w, out_h, out_w):
+    """-> (out_h, out_w) as ints; ValueError for a size below 1 or an axis that shrinks by more than RESIZE_MAX_RATIO."""
+    in_h, in_w, out_h, out_w = int(in_h), int(in_w), int(out_h), int(out_w)
+    if min(in_h, in_w, out_h, out_w) < 1:
+        raise ValueError("larvanet_amd: resizing needs sizes >= 1, got %d x %d -> %d x %d (height x width)"
+                         % (in_h, in_w, out_h, out_w))
+    if in_h > RESIZE_MAX_RATIO * out_h or in_w > RESIZE_MAX_RATIO * out_w:
+        raise ValueError("larvanet_amd: resizing shrinks an axis by at most %d, got %d x %d -> %d x %d (height x width)"
+                         % (RESIZE_MAX_RATIO, in_h, in_w, out_h, out_w))
+    return out_h, out_w
+
+
+def parse_output_size(text):
+    """'WxH' (the --output_size of the drivers, e.g. 1920x1080) -> (height, width); ValueError for anything else."""
+    parts = str(text).lower().split("x")
+    if len(parts) != 2 or not all(p.isdigit() for p in parts) or int(parts[0]) < 1 or int(parts[1]) < 1:
+        raise ValueError("larvanet_amd: --output_size takes WIDTHxHEIGHT with both >= 1 (e.g. 1920x1080), got %r" % (text,))
+    return int(parts[1]), int(parts[0])
+
+
+def check_output_size(output_size, in_h, in_w):
+    """The output_size argument of the image entry points against the network's (in_h, in_w) result -> None, or
+    (height, width) as ints; TypeError / ValueError for anything else."""
+    if output_size is None:
+        return None
+    if isinstance(output_size, (str, bytes)) or not hasattr(output_size, "__len__") or len(output_size) != 2:
+        raise TypeError("larvanet_amd: output_size is (height, width) or None, got %r" % (output_size,))
+    h, w = output_size
+    if int(h) != h or int(w) != w:
+        raise TypeError("larvanet_amd: output_size is (height, width) in whole pixels, got %r" % (output_size,))
+    return check_resize(in_h, in_w, h, w)
+
+
+def _keys_cubic(x):
+    a = -0.5
+    x = np.abs(x)
+    near = ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0
+    far = (((x - 5.0) * x + 8.0) * x - 4.0) * a
+    return np.where(x < 1.0, near, np.where(x < 2.0, far, 0.0))
+
+
+def resize_coeffs(n_in, n_out):
+    """One axis of the resize -> (bounds int32 [n_out][2] = (lo, n), coeffs int32 [n_out][ksize], zero beyond n)."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError("larvanet_amd: resizing needs sizes >= 1, got %d -> %d" % (n_in, n_out))
+    if n_in > RESIZE_MAX_RATIO * n_out:
+        raise ValueError("larvanet_amd: resizing shrinks an axis by at most %d, got %d -> %d" % (RESIZE_MAX_RATIO, n_in, n_out))
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = 2.0 * fs
+    ksize = 2 * int(np.ceil(support)) + 1
+    bounds = np.zeros((n_out, 2), np.int32)
+    coeffs = np.zeros((n_out, ksize), np.int32)
+    inv = 1.0 / fs
+    for i in range(n_out):
+        c = (i + 0.5) * scale
+        lo = max(int(c - support + 0.5), 0)
+        n = min(int(c + support + 0.5), n_in) - lo
+        k = _keys_cubic((np.arange(n, dtype=np.float64) + lo - c + 0.5) * inv)
+        total = 0.0
+        for v in k:   # (index order: the sum Pillow divides by)
+            total += float(v)
+        if total != 0.0:
+            k = k / total
+        k = k * float(1 << RESIZE_PRECISION_BITS)
+        bounds[i] = (lo, n)
+        coeffs[i, :n] = np.where(k < 0, k - 0.5, k + 0.5).astype(np.int64)   # (astype truncates towards zero, as (int))
+    return bounds, coeffs
+
+
+def _resize_axis0(a, n_out):
+    """One pass along axis 0 of the uint8 array a -> uint8."""
+    bounds, coeffs = resize_coeffs(a.shape[0], n_out)
+    lo = bounds[:, 0].astype(np.int64)
+    acc = np.full((n_out,) + a.shape[1:], 1 << (RESIZE_PRECISION_BITS - 1), np.int32)
+    tail = (1,) * (a.ndim - 1)
+    for j in range(coeffs.shape[1]):   # (a tap beyond n has weight 0: its clamped index reads a pixel that counts for nothing)
+        acc += a[np.minimum(lo + j, a.shape[0] - 1)].astype(np.int32) * coeffs[:, j].reshape((n_out,) + tail)
+    return np.clip(acc >> RESIZE_PRECISION_BITS, 0, 255).astype(np.uint8)
+
+
+def resize_u8(image, out_h, out_w):
+    """uint8 (H, W, 3) -> uint8 (out_h, out_w, 3): Pillow's Image.resize((out_w, out_h), Image.BICUBIC) byte for byte (the
+    definition above).  ValueError for a size below 1 or an axis that shrinks by more than 4."""
+    if not isinstance(image, np.ndarray) or image.dtype != np.uint8:
+        raise TypeError("larvanet_amd: resize_u8 takes a uint8 numpy array, got %s"
+                        % (getattr(image, "dtype", type(image).__name__),))
+    if image.ndim != 3 or image.shape[2] != 3:
+        raise ValueError("larvanet_amd: resize_u8 takes an (H, W, 3) image, got shape %s" % (image.shape,))
+    out_h, out_w = check_resize(image.shape[0], image.shape[1], out_h, out_w)
+    a = image
+    if out_w != a.shape[1]:
+        a = np.swapaxes(_resize_axis0(np.swapaxes(a, 0, 1), out_w), 0, 1)
+    if out_h != a.shape[0]:
+        a = _resize_axis0(a, out_h)
+    return np.ascontiguousarray(a)
+
+
 # ------------------------------------------------------------------ planar YUV 4:2:0 (I420) <-> RGB, in exact integers
 # A frame is ONE contiguous uint8 buffer: Y [H][W], then U [ch][cw], then V [ch][cw], cw = (W + 1) // 2, ch = (H + 1) // 2.
 # Odd W and H are legal; a coordinate outside a plane is the edge's (clamped), reading and writing.  Chroma is centred on

@@ -1371,3 +1371,61 @@ def rgb_u8_to_i420(x, matrix="bt601", full_range=False, out=None):
     hip_lib.check(lib.larva_rgb_u8_to_i420(x.data_ptr(), out.data_ptr(), pitch, N, H, W, table, _stream()),
                   "larva_rgb_u8_to_i420")
     return out
+
+
+# ------------------------------------------------------------------ bicubic resize to any size (csrc/larva_resize.hip)
+RESIZE_TILE_ROWS = 16    # a workgroup's tile: 16 output rows x 32 output pixels (kResizeRows / kResizeCols of the kernel)
+RESIZE_TILE_COLS = 32
+_RESIZE_TABLES = {}      # (n_in, n_out, device) -> (bounds, coeffs, ksize) on the device; a few entries per video or folder
+_RESIZE_TABLES_MAX = 64
+
+
+def _resize_tables(n_in, n_out, device):
+    """The device tables of one axis (image_utils.resize_coeffs), cached; (None, None, 0) for an axis that keeps its size."""
+    if n_in == n_out:
+        return None, None, 0
+    key = (n_in, n_out, str(device))
+    hit = _RESIZE_TABLES.get(key)
+    if hit is None:
+        from .image_utils import resize_coeffs
+        bounds, coeffs = resize_coeffs(n_in, n_out)
+        while len(_RESIZE_TABLES) >= _RESIZE_TABLES_MAX:
+            _RESIZE_TABLES.pop(next(iter(_RESIZE_TABLES)))
+        hit = (torch.from_numpy(bounds).to(device), torch.from_numpy(coeffs).to(device), int(coeffs.shape[1]))
+        _RESIZE_TABLES[key] = hit
+    return hit
+
+
+def resize_u8(x_u8_hwc, out_h, out_w, out=None):
+    """uint8 [N][H][W][3] (or one image [H][W][3]) on the device -> uint8 [N][out_h][out_w][3] ([out_h][out_w][3]): Pillow's
+    Image.resize((out_w, out_h), Image.BICUBIC) per image (image_utils.resize_u8, byte for byte), both passes in one launch.
+    An axis shrinks by at most 4 (ValueError beyond); any upsampling.  `out`: a contiguous uint8 tensor of the result's
+    shape to fill."""
+    from .image_utils import check_resize
+    lib = hip_lib.load()
+    x = x_u8_hwc
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("larvanet_amd: x must be a uint8 tensor, got %s" % type(x).__name__)
+    if x.dtype != torch.uint8:
+        raise TypeError("larvanet_amd: x must be a uint8 tensor, got %s" % x.dtype)
+    if x.dim() not in (3, 4) or int(x.shape[-1]) != 3 or min(x.shape) < 1:
+        raise ValueError("larvanet_amd: x must be [N][H][W][3] or [H][W][3], got %s" % (tuple(x.shape),))
+    H, W = int(x.shape[-3]), int(x.shape[-2])
+    N = int(x.shape[0]) if x.dim() == 4 else 1
+    h, w = check_resize(H, W, out_h, out_w)
+    if not x.is_cuda:
+        raise RuntimeError("larvanet_amd: x must be a tensor on a HIP device (no CPU path exists)")
+    if not x.is_contiguous():
+        raise RuntimeError("larvanet_amd: x must be contiguous (strides %s)" % (tuple(x.stride()),))
+    shape = tuple(x.shape[:-3]) + (h, w, 3)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.uint8)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != shape
+          or out.device != x.device or not out.is_contiguous()):
+        raise RuntimeError("larvanet_amd: out must be a contiguous uint8 %s tensor on the input's device" % (list(shape),))
+    hb, hc, kx = _resize_tables(W, w, x.device)
+    vb, vc, ky = _resize_tables(H, h, x.device)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    hip_lib.check(lib.larva_resize_u8(x.data_ptr(), out.data_ptr(), N, H, W, h, w, ptr(hb), ptr(hc), kx, ptr(vb), ptr(vc), ky,
+                                      _stream()), "larva_resize_u8")
+    return out

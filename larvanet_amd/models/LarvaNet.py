@@ -26,7 +26,7 @@ from ..autograd import step_prologue as autograd_step_prologue
 from ..captured_step import CapturedStep, LossCopy
 from ..infer_graphs import Form, GraphTable
 from ..optim import FlatAdamW, flatten_parameters
-from ..image_utils import YUV_MATRICES, i420_frame_bytes
+from ..image_utils import YUV_MATRICES, check_output_size, i420_frame_bytes
 from ..metrics import image_psnr, image_to_uint8, fit_truth_image_size
 from .base import BaseModel
 
@@ -1072,21 +1072,38 @@ class LarvaNet(BaseModel):
             _require_hip(x_u8)
         return x_u8.contiguous()
 
-    def upscale_u8(self, input_list, scale):
+    def _output_size(self, output_size, height, width):
+        """The output_size argument of the image entry points for a height x width input -> None or (h, w), checked against
+        the network's (s height) x (s width) result (image_utils.check_output_size) before any device work."""
+        return check_output_size(output_size, self.scale * int(height), self.scale * int(width))
+
+    def _infer_sized(self, x, size):
+        """_infer_checked(x, u8=True); with size = (h, w) resized to it on the device (kernels.resize_u8: one eager launch
+        on the forward's stream behind the replayed or eager forward, into a tensor of its own)."""
+        out = self._infer_checked(x, u8=True)
+        return out if size is None else K.resize_u8(out, size[0], size[1])
+
+    def upscale_u8(self, input_list, scale, output_size=None):
         """list of uint8 (H, W, 3) images of one shape -> uint8 (N, sH, sW, 3) numpy:
         image_to_uint8(upscale(...)) byte for byte, transposed for an image writer, with a quarter of the bytes crossing
-        the host link and no pass over the image on the host."""
+        the host link and no pass over the image on the host.  output_size = (height, width): each image resized to it on
+        the device before it leaves (image_utils.resize_u8 of today's result, byte for byte) -> (N, height, width, 3)."""
         batch = self._check_u8_images(input_list, scale)
+        size = self._output_size(output_size, batch.shape[1], batch.shape[2])
         with torch.no_grad():
             x = torch.from_numpy(batch).to(self.device)
             _require_hip(x)
-            return self._infer_checked(x, u8=True).cpu().numpy()
+            return self._infer_sized(x, size).cpu().numpy()
 
-    def upscale_u8_tensor(self, x_u8):
-        """upscale_u8 without the trips to and from the host: uint8 [N][H][W][3] on self.device -> uint8 [N][sH][sW][3]."""
-        x = self._check_u8_tensor(x_u8)
+    def upscale_u8_tensor(self, x_u8, output_size=None):
+        """upscale_u8 without the trips to and from the host: uint8 [N][H][W][3] on self.device -> uint8 [N][sH][sW][3], or
+        [N][height][width][3] with output_size = (height, width)."""
+        x = self._check_u8_tensor(x_u8, on_device=False)
+        size = self._output_size(output_size, x.shape[1], x.shape[2])
+        _require_hip(x)
         with torch.no_grad():
-            return self._infer_checked(x, u8=True).clone()
+            out = self._infer_sized(x, size)
+            return out.clone() if size is None else out
 
     def evaluate_u8_tensor(self, x_u8, truth_u8, shave=None, channel="y", ssim=True):
         """Upscale and score on the device: x_u8 uint8 [N][H][W][3] and truth_u8 uint8 [N][th][tw][3] (th >= sH, tw >= sW,
@@ -1121,12 +1138,15 @@ class LarvaNet(BaseModel):
         width, height = int(width), int(height)
         return width, height, i420_frame_bytes(width, height)
 
-    def upscale_yuv420_tensor(self, buf_u8, width, height, matrix="bt601", full_range=False):
+    def upscale_yuv420_tensor(self, buf_u8, width, height, matrix="bt601", full_range=False, output_size=None):
         """uint8 [N][frame bytes] on self.device, N I420 frames of width x height (image_utils.i420_frame_bytes) ->
         uint8 [N][HR frame bytes], the frames of (s width) x (s height).  Byte for byte
         rgb_u8_to_i420(f32_chw_to_u8_hwc(forward(i420_to_rgb_f32(frame)))) of image_utils, forward the inference at this
-        model's precision (fp16 overflow raises FloatingPointError; --self_ensemble is honoured)."""
+        model's precision (fp16 overflow raises FloatingPointError; --self_ensemble is honoured).  output_size = (height,
+        width): the uint8 RGB image goes through image_utils.resize_u8 before rgb_u8_to_i420, and the frames are of that
+        size (odd sizes included)."""
         width, height, nbytes = self._check_yuv_args(width, height, matrix, full_range)
+        size = self._output_size(output_size, height, width)
         if not isinstance(buf_u8, torch.Tensor) or buf_u8.dtype != torch.uint8:
             raise TypeError("larvanet_amd: upscale_yuv420_tensor takes a uint8 tensor, got %s"
                             % (getattr(buf_u8, "dtype", type(buf_u8).__name__),))
@@ -1136,12 +1156,14 @@ class LarvaNet(BaseModel):
         _require_hip(buf_u8)
         with torch.no_grad():   # (the two conversions are launches of their own, outside the forward's cached graph)
             x = K.i420_to_rgb_f32(buf_u8.contiguous(), width, height, matrix, bool(full_range))
-            return K.rgb_u8_to_i420(self._infer_checked(x, u8=True), matrix, bool(full_range))
+            return K.rgb_u8_to_i420(self._infer_sized(x, size), matrix, bool(full_range))
 
-    def upscale_yuv420(self, frames, scale, width, height, matrix="bt601", full_range=False):
+    def upscale_yuv420(self, frames, scale, width, height, matrix="bt601", full_range=False, output_size=None):
         """list of uint8 1-D numpy I420 frames of width x height -> list of the uint8 1-D HR frames of (s width) x
-        (s height): upscale_yuv420_tensor with the trips over the host link, 1.5 bytes per pixel each way."""
+        (s height), or of output_size = (height, width): upscale_yuv420_tensor with the trips over the host link, 1.5
+        bytes per pixel each way."""
         width, height, nbytes = self._check_yuv_args(width, height, matrix, full_range, scale)
+        self._output_size(output_size, height, width)
         if isinstance(frames, np.ndarray) or not len(frames):
             raise ValueError("larvanet_amd: upscale_yuv420 takes a non-empty list of 1-D uint8 frames")
         for f in frames:
@@ -1153,7 +1175,7 @@ class LarvaNet(BaseModel):
                                  "got shape %s" % (width, height, nbytes, f.shape,))
         buf = torch.from_numpy(np.ascontiguousarray(np.stack(frames))).to(self.device)
         _require_hip(buf)
-        return list(self.upscale_yuv420_tensor(buf, width, height, matrix, full_range).cpu().numpy())
+        return list(self.upscale_yuv420_tensor(buf, width, height, matrix, full_range, output_size).cpu().numpy())
 
     # ------------------------------------------------------------------ every exit's image from one forward pass
     def _check_exits(self):

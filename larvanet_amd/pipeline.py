@@ -23,6 +23,10 @@ pinned or copied.
 upscale_yuv_stream() is the same pipeline over planar YUV 4:2:0 video frames: a frame travels in and out as its 1.5 bytes
 per pixel, and the two colour conversions (kernels.i420_to_rgb_f32 / rgb_u8_to_i420) are two launches on the compute
 stream around the forward, the second one writing straight into the slot's output buffer.
+
+With output_size = (height, width) both upscaling streams resize every result to that one size on the device
+(kernels.resize_u8, one eager launch on the compute stream behind the forward; for video between the forward's uint8 RGB
+image and rgb_u8_to_i420): the slot's output buffers, and what crosses the host link on the way back, have the target size.
 """
 import collections
 
@@ -97,20 +101,29 @@ def _check_image(a, who="upscale_stream"):
         raise ValueError("larvanet_amd: %s takes (H, W, 3) images, got shape %s" % (who, a.shape,))
 
 
-def upscale_stream(model, images, scale, depth=2):
+def _check_target(output_size):
+    """output_size as given -> None or (height, width); the ratio is checked per image, its size being known only then."""
+    from .image_utils import check_output_size
+    return None if output_size is None else check_output_size(output_size, 1, 1)
+
+
+def upscale_stream(model, images, scale, depth=2, output_size=None):
     """Generator: uint8 (H, W, 3) numpy images of any sizes -> their uint8 (sH, sW, 3) upscaled images, in input order;
     each result equals model.upscale_u8([image], scale)[0].  At most `depth` images are in flight (depth 1 = no overlap).
+    output_size = (height, width): every result is resized to it on the device and equals model.upscale_u8([image], scale,
+    output_size=output_size)[0]; an image the size is out of range for raises ValueError before anything of it is launched.
     Under --precision fp16 an image whose activations overflow raises FloatingPointError when its turn to be yielded
     comes; the images before it have been yielded.  The yielded arrays are the caller's (copies of the pinned staging
     buffers)."""
     depth = int(depth)
     if depth < 1:
         raise ValueError("larvanet_amd: upscale_stream needs depth >= 1")
+    target = _check_target(output_size)
     if int(scale) != model.scale:
         raise ValueError("larvanet_amd: this model upscales by %d, not by %r" % (model.scale, scale))
     if model.device.type != "cuda":
         raise RuntimeError("larvanet_amd: upscale_stream only runs on a HIP device (MI355X); there is no CPU fallback")
-    return _stream(model, images, depth)
+    return _stream(model, images, depth, target=target)
 
 
 def evaluate_stream(model, pairs, scale, shave=None, channel="y", ssim=True, depth=2, keep_images=False):
@@ -149,15 +162,20 @@ def _check_frame(f, nbytes, width, height):
                          % (width, height, nbytes, f.shape,))
 
 
-def upscale_yuv_stream(model, frames, scale, width=None, height=None, matrix="bt601", full_range=False, depth=2):
+def upscale_yuv_stream(model, frames, scale, width=None, height=None, matrix="bt601", full_range=False, depth=2,
+                       output_size=None):
     """Generator: uint8 1-D numpy I420 frames of width x height -> their uint8 1-D HR frames of (s width) x (s height), in
     input order; each equals model.upscale_yuv420([frame], scale, width, height, matrix, full_range)[0].  With width and
     height None the items are (frame, width, height) triples of any mix of sizes.  upscale_stream's pipeline: pinned
     staging slots, one copy stream, at most `depth` frames in flight; under --precision fp16 a frame whose activations
-    overflow raises FloatingPointError when its turn to be yielded comes, the frames before it have been yielded."""
+    overflow raises FloatingPointError when its turn to be yielded comes, the frames before it have been yielded.
+    output_size = (height, width): the HR frames are of that size, as upscale_yuv420's with the same argument."""
     depth = int(depth)
     if depth < 1:
         raise ValueError("larvanet_amd: upscale_yuv_stream needs depth >= 1")
+    target = _check_target(output_size)
+    if width is not None and height is not None:
+        model._output_size(target, height, width)   # (one input size: the ratio is refused here, before any frame)
     if (width is None) != (height is None):
         raise ValueError("larvanet_amd: upscale_yuv_stream takes width and height, or neither (items are then "
                          "(frame, width, height) triples)")
@@ -165,13 +183,14 @@ def upscale_yuv_stream(model, frames, scale, width=None, height=None, matrix="bt
     if model.device.type != "cuda":
         raise RuntimeError("larvanet_amd: upscale_yuv_stream only runs on a HIP device (MI355X); there is no CPU fallback")
     size = None if width is None else (int(width), int(height))
-    return _stream(model, frames, depth, yuv={"size": size, "matrix": matrix, "full_range": bool(full_range)})
+    return _stream(model, frames, depth, yuv={"size": size, "matrix": matrix, "full_range": bool(full_range)}, target=target)
 
 
-def _stream(model, images, depth, score=None, yuv=None):
+def _stream(model, images, depth, score=None, yuv=None, target=None):
     """The pipeline of upscale_stream; with `score` (evaluate_stream's settings) the items are (input, truth) pairs; with
-    `yuv` (upscale_yuv_stream's settings) they are I420 frames, or (frame, width, height) triples."""
-    if score is not None or yuv is not None:
+    `yuv` (upscale_yuv_stream's settings) they are I420 frames, or (frame, width, height) triples; with `target` = (height,
+    width) the two upscaling streams resize every result to it."""
+    if score is not None or yuv is not None or target is not None:
         from . import kernels as K
     if yuv is not None:
         from .image_utils import i420_frame_bytes
@@ -221,9 +240,11 @@ def _stream(model, images, depth, score=None, yuv=None):
                     image, fw, fh = (image,) + yuv["size"] if yuv["size"] is not None else image
                     fw, fh = int(fw), int(fh)
                     _check_frame(image, i420_frame_bytes(fw, fh), fw, fh)
+                    model._output_size(target, fh, fw)
                     image = image[None]   # (a batch of one frame: [1][frame bytes])
                 elif score is None:
                     _check_image(image)
+                    model._output_size(target, image.shape[0], image.shape[1])
                 else:
                     image, truth = image
                     _check_image(truth, "evaluate_stream")
@@ -261,13 +282,19 @@ def _stream(model, images, depth, score=None, yuv=None):
                 if yuv is not None:   # frame -> float planes -> forward -> HR frame, written into the slot's own buffer
                     x = K.i420_to_rgb_f32(dev_in[0], fw, fh, yuv["matrix"], yuv["full_range"])
                     out = model._infer_u8_images(x)
-                    slot.out_shape = (1, 1, i420_frame_bytes(model.scale * fw, model.scale * fh))
+                    if target is not None:
+                        out = K.resize_u8(out, target[0], target[1])
+                    slot.out_shape = (1, 1, i420_frame_bytes(out.shape[2], out.shape[1]))
                     K.rgb_u8_to_i420(out, yuv["matrix"], yuv["full_range"], out=slot.views_out(slot.out_shape)[1][0])
                 else:
                     out = model._infer_u8_images(dev_in)   # (the x8 self-ensemble under --self_ensemble)
-                    slot.out_shape = tuple(out.shape)
-                    if keep:
-                        slot.views_out(slot.out_shape)[1].copy_(out)
+                    if target is not None:   # (upscale_stream only: resized straight into the slot's own buffer)
+                        slot.out_shape = (1,) + target + (3,)
+                        K.resize_u8(out, target[0], target[1], out=slot.views_out(slot.out_shape)[1])
+                    else:
+                        slot.out_shape = tuple(out.shape)
+                        if keep:
+                            slot.views_out(slot.out_shape)[1].copy_(out)
                 if score is not None:   # (scored where the forward left it: nothing else runs on this stream in between)
                     K.u8_metrics(out[0], dev_truth, score["shave"], score["channel"], score["ssim"],
                                  result=slot.records(K.METRIC_RESULT_WORDS)[1])

@@ -3,7 +3,11 @@ is written as <output_path>/<stem>.png.
 
     python -m larvanet_amd.upscale_images --model=LarvaNet --num_modules=4 --num_blocks=4,4,4,4 \\
         --restore_path=model.pth --input_path=LR --output_path=SR [--precision fp16] [--self_ensemble]
-        [--io_threads 8] [--all_exits]
+        [--io_threads 8] [--all_exits] [--output_size 1920x1080]
+
+--output_size WxH writes every image at exactly that size instead of the network's integer multiple: the upscaled image is
+resized on the device before it leaves it (Pillow's bicubic, byte for byte: image_utils.resize_u8).  An axis may shrink
+by at most 4 from the network's output; the PNG headers are checked against that before any image is decoded.
 
 --all_exits writes every exit of the multi-exit network from ONE forward pass per image, as <stem>_exit<k>.png with k
 counted from 1 like --leg (model.upscale_exits_u8): the head and the bodies run once, the legs go out together.  It runs
@@ -26,6 +30,7 @@ import time
 import numpy as np
 
 from . import dist as ldist
+from .image_utils import check_resize, parse_output_size
 
 
 def build_parser():
@@ -45,7 +50,26 @@ def build_parser():
     p.add_argument("--all_exits", action="store_true",
                    help="write every exit's image from one forward pass per image, as <stem>_exit<k>.png (k from 1, like "
                         "--leg); runs image by image, not through the copy-overlapped stream; LarvaNet / LarvaLeg only")
+    p.add_argument("--output_size", type=str, default=None,
+                   help="WIDTHxHEIGHT of the written images (e.g. 1920x1080): the upscaled image is resized on the device "
+                        "(bicubic, Pillow's bytes); default: scale times the input size")
     return p
+
+
+def output_size_of(args):
+    """--output_size as (height, width), or None; ValueError for a malformed value or together with --all_exits."""
+    if args.output_size is None:
+        return None
+    if args.all_exits:
+        raise ValueError("larvanet_amd.upscale_images: --output_size together with --all_exits is not supported")
+    return parse_output_size(args.output_size)
+
+
+def png_size(path):
+    """(height, width) from the file's header, without decoding it."""
+    from PIL import Image
+    with Image.open(path) as im:
+        return im.size[1], im.size[0]
 
 
 def list_pngs(input_path):
@@ -100,6 +124,7 @@ def _prefetched(pool, fn, items, ahead):
 
 def main(argv=None):
     args, remaining = build_parser().parse_known_args(argv)
+    target = output_size_of(args)
     if args.cuda_device is not None and "LOCAL_RANK" not in os.environ:
         os.environ["HIP_VISIBLE_DEVICES"] = args.cuda_device
     rank, world = ldist.init_from_env()
@@ -111,6 +136,10 @@ def main(argv=None):
     if not mine:
         print("finished")
         return {}
+    if target is not None:   # (a ratio beyond 4: refused from the headers, before any image is decoded)
+        for name in mine:
+            in_h, in_w = png_size(os.path.join(args.input_path, name))
+            check_resize(in_h * args.scale, in_w * args.scale, *target)
 
     from . import pipeline
     print("prepare model - %s" % args.model)
@@ -150,7 +179,7 @@ def main(argv=None):
     with concurrent.futures.ThreadPoolExecutor(max_workers=threads) as pool:
         decoded = _prefetched(pool, read_rgb, [os.path.join(args.input_path, n) for n in mine], ahead=threads + args.depth)
         last = time.perf_counter()
-        for i, out in enumerate(pipeline.upscale_stream(model, decoded, args.scale, depth=args.depth)):
+        for i, out in enumerate(pipeline.upscale_stream(model, decoded, args.scale, depth=args.depth, output_size=target)):
             now = time.perf_counter()
             durations[mine[i]] = now - last   # (time between results: the stream's rate, not one image's latency)
             writes.append(pool.submit(write_rgb, out, os.path.join(args.output_path, output_name(mine[i]))))

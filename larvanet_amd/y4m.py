@@ -57,6 +57,10 @@ class Header:
         return Header(self.width * scale, self.height * scale, self.fps, self.interlace, self.aspect, self.chroma,
                       self.comments)
 
+    def resized(self, width, height):
+        """The header of the stream resized to width x height: W and H replaced, every other tag kept."""
+        return Header(width, height, self.fps, self.interlace, self.aspect, self.chroma, self.comments)
+
     def to_bytes(self):
         tags = ["W%d" % self.width, "H%d" % self.height]
         tags += [t + v for t, v in (("F", self.fps), ("I", self.interlace), ("A", self.aspect), ("C", self.chroma))
