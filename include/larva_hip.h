@@ -65,7 +65,11 @@ int larva_step_prologue(const float* const* w, float* const* wpk_fwd, float* con
  * channel-concatenated input.  cout in {32, 48, 64}.
  * Epilogue order: +bias -> relu -> (mask > 0 ? v : 0) -> +res0 -> +res1.
  * mode 0: out [N][cout][H][W]; supported fusions: none | relu | mask | res0 | res0+res1.
- * mode 1: out [N][cout/16][4H][4W] = PixelShuffle(4)(conv) (+ base, same shape, may be NULL). */
+ * mode 1: out [N][cout/16][4H][4W] = PixelShuffle(4)(conv) (+ base, same shape, may be NULL).
+ * Alignment.  pitch % 4 == 0 with wpk, every src, the mode-0 out, res0, res1 and mask 16-byte aligned takes the 16-byte
+ * staging path; anything else (4-byte aligned) a register-staged path with the same results bit for bit.  bias: any
+ * 4-byte boundary.  mode 1 moves four HR pixels per access on every path: `out` and `base` must be 16-byte aligned
+ * (hipErrorInvalidValue otherwise, from every entry point that takes a mode). */
 int larva_conv3x3_fwd(const float* const* src, int n_src, int cin_per_src, const float* wpk,
                       const float* bias, const float* res0, const float* res1, const float* mask,
                       const float* base, float* out, int N, int cout, int H, int W, int relu,
@@ -106,7 +110,7 @@ int larva_head_conv3_direct(const float* x, const float* w, const float* bias, f
  * (sign(0) = 0) in the pixel-unshuffled layout [N][cout][H][pitch]; out[j] ([N][cout/16][4H][4W])
  * may be NULL when the image itself is not wanted.  Replaces larva_conv3x3_fwd_batch(mode 1) +
  * larva_l1_partial_grad_batch: one launch and four 14 MB sweeps less per step.  cout 48, 16-byte
- * staging path only (801 otherwise). */
+ * staging path only, and base, truth, grad and out 16-byte aligned (801 otherwise). */
 int larva_exit_l1_partials(int N, int H, int pitch);
 int larva_conv3x3_exit_l1_batch(int njobs, const float* const* src, int n_src, int cin_per_src,
                                 const float* const* wpk, const float* const* bias, const float* const* base,
@@ -156,7 +160,11 @@ int larva_conv3x3_fwd_tiled(const float* const* src, int n_src, int cin_per_src,
  * [N][cout][H][W] and x[i] [N][cin][H][W], uses partial[i] (larva_wgrad_partial_floats()
  * floats) as workspace and OVERWRITES dw[i] ([cout][w_cin_total[i]][3][3], channels
  * [cin_off[i], cin_off[i]+cin_valid[i])) and db[i] ([cout], may be NULL).
- * (cout, cin) in {(48,48), (48,16), (32,32), (64,64)}.  Deterministic (no atomics). */
+ * (cout, cin) in {(48,48), (48,16), (32,32), (64,64)}.  Deterministic (no atomics).
+ * Alignment.  dy and x: W % 4 == 0 and 16-byte aligned pointers take 16-byte loads, anything else (4-byte aligned) a
+ * narrower walk with the same results; the flat grid has only the former (hipErrorNotSupported).  partial[i] (and
+ * head_partial) is written and reduced 16 bytes per lane on every path: 16-byte aligned, hipErrorInvalidValue
+ * otherwise, from every entry point that takes it.  dw and db: any 4-byte boundary. */
 long long larva_wgrad_partial_floats(int cout, int cin, int splits);
 /* Workgroups of the (cout, cin) weight-gradient kernel that share a CU (1 or 2: the small shapes -- (32,32), the (C,16)
  * heads -- fit twice and hide each other's staging phases): launch 256 * this many workgroups in total to fill the chip. */
@@ -209,7 +217,8 @@ int larva_wgrad_reduce_with_loss(const float* const* partial, float* const* dw, 
 
 /* ---- base image -----------------------------------------------------------------------------
  * F.interpolate(x, scale_factor=4, mode='bicubic', align_corners=False), models/LarvaNet.py:283-285.
- * in [N][C][H][W] -> out [N][C][4H][4W]. */
+ * in [N][C][H][W] -> out [N][C][4H][4W].  An `out` that is not 16-byte aligned is written with 4-byte stores (the same
+ * values bit for bit). */
 int larva_bicubic4_fwd(const float* in, float* out, int N, int C, int H, int W, void* stream);
 /* F.interpolate(x, scale_factor=4, mode, align_corners=False) for the modes with which the reference's call
  * (models/LarvaNet.py:57,283-285) does not raise: mode 0 bicubic (as above), 1 bilinear.  out 16-byte aligned. */
@@ -264,7 +273,8 @@ int larva_l1_partial_grad_batch(const float* const* a, const float* b, int n, fl
                                 float* const* partial, int* blocks_out, float* const* grad, int N, int C, int H,
                                 int W, void* stream);
 
-/* ---- PixelShuffle(4) backward (models/LarvaNet.py:261): in [N][C][4H][4W] -> out [N][16C][H][W] */
+/* ---- PixelShuffle(4) backward (models/LarvaNet.py:261): in [N][C][4H][4W] -> out [N][16C][H][W]; `in` 16-byte aligned
+ * (hipErrorInvalidValue otherwise) */
 int larva_pixel_unshuffle4(const float* in, float* out, int N, int C, int H, int W, void* stream);
 
 /* ---- x2 / x3 (csrc/larva_scale.hip) ---------------------------------------------------------
@@ -358,6 +368,10 @@ int larva_u8_metrics(const unsigned char* out, long long out_pitch, const unsign
  * uint16_t bit images of IEEE half, CHANNELS-LAST [N][H][W][48] (not the fp32 NCHW of the entry points above); images
  * and bases stay fp32 NCHW.  `flag` is one device unsigned that an fp16-storing launch sets to 1 (never clears) when a
  * value is not finite or exceeds 65504 in magnitude before it is rounded; the caller zeroes it.
+ * Alignment (there is no narrower walk: hipErrorInvalidValue before any launch otherwise).  16 bytes: every fp16
+ * activation (srcs, res0, res1, out, the head's out), every packed weight image, the fp32 bias of the conv entry points,
+ * the fp32 base and fp32 HR out.  4 bytes: the uint8 HR out.  Any boundary their type allows: the head's x, w and bias,
+ * the fp32 weight larva_f16_pack_weights reads, and flag.
  *
  * larva_f16_packed_weight_halves(48, 48 m) = m * 14 * 3 * 64 * 8 (m <= 8; -1 for any other shape): the A-operand image of
  * a [48][48 m][3][3] fp32 weight, [src m][K-step 14][M tile 3][lane 64][8] halves, K = (tap, 8-channel group), rounded to

@@ -330,7 +330,23 @@ static bool shape_ok(int N, int H, int W, int njobs = 1) {
          (tiles_of(N, H, W) + 7) / 8 * 8 * njobs < (1ll << 31);
 }
 
+// What the kernels access wide, and so what the launchers refuse (hipErrorInvalidValue) before anything is launched:
+// fp16 activations (sources, residuals, outputs), packed weight images, the conv kernels' fp32 bias, the fp32 base and
+// HR output images are moved 16 bytes at a time (a residual and a conv output 8, held to the same rule: an output is the
+// next layer's source); the uint8 HR image is written as three 4-byte words per lane.  The head's image, weights and
+// bias and the overflow flag are accessed one element at a time: any address their type allows.
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+static bool conv_ptrs_ok(const ConvArgs& a) {
+  for (int i = 0; i < a.nsrc; ++i)
+    if (!aligned16(a.src[i])) return false;
+  return aligned16(a.wpk) && aligned16(a.bias) && aligned16(a.res0) && aligned16(a.res1) && aligned16(a.out) &&
+         aligned16(a.base) && aligned16(a.out_hr) && aligned4(a.out_u8);
+}
+
 static int launch_conv(int epi, ConvArgs& a, int N, hipStream_t s) {
+  if (!conv_ptrs_ok(a)) return (int)hipErrorInvalidValue;
   a.tiles_x = (a.W + kCols - 1) / kCols;
   a.tiles_y = (a.H + kRows - 1) / kRows;
   const dim3 grid((unsigned)((long long)N * a.tiles_x * a.tiles_y)), block(256);
@@ -352,9 +368,13 @@ static int launch_jobs(int epi, int njobs, const uint16_t* const* srcs, const ui
                        int W, hipStream_t s) {
   if (njobs < 1 || njobs > kMaxJobs || !srcs || !wpks || !biases || !outs || !shape_ok(N, H, W, njobs))
     return (int)hipErrorInvalidValue;
+  if (!aligned16(base)) return (int)hipErrorInvalidValue;
   JobArgs a = {};
   for (int j = 0; j < njobs; ++j) {
     if (!srcs[j] || !wpks[j] || !biases[j] || !outs[j]) return (int)hipErrorInvalidValue;
+    if (!aligned16(srcs[j]) || !aligned16(wpks[j]) || !aligned16(biases[j]) ||
+        !(epi == EPI_SHUFFLE_U8 ? aligned4(outs[j]) : aligned16(outs[j])))
+      return (int)hipErrorInvalidValue;
     a.src[j] = srcs[j];
     a.wpk[j] = wpks[j];
     a.bias[j] = biases[j];
@@ -392,7 +412,7 @@ long long larva_f16_packed_weight_halves(int cout, int cin) {
 
 int larva_f16_pack_weights(const float* w, uint16_t* wpk, int cout, int cin, void* stream) {
   const long long halves = larva_f16_packed_weight_halves(cout, cin);
-  if (!w || !wpk || halves < 0) return (int)hipErrorInvalidValue;
+  if (!w || !wpk || halves < 0 || !aligned16(wpk)) return (int)hipErrorInvalidValue;
   const int frags = (int)(halves / 8);
   hipLaunchKernelGGL(pack_kernel, dim3((frags + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, wpk, cin / kC);
   return (int)hipGetLastError();
@@ -400,7 +420,7 @@ int larva_f16_pack_weights(const float* w, uint16_t* wpk, int cout, int cin, voi
 
 int larva_f16_head(const float* x, const float* w, const float* bias, uint16_t* out, unsigned* flag, int N, int H,
                    int W, void* stream) {
-  if (!x || !w || !bias || !out || !flag || !shape_ok(N, H, W)) return (int)hipErrorInvalidValue;
+  if (!x || !w || !bias || !out || !flag || !shape_ok(N, H, W) || !aligned16(out)) return (int)hipErrorInvalidValue;
   const long long px = (long long)N * H * W;
   hipLaunchKernelGGL(head_kernel, dim3((unsigned)((px + 255) / 256), 3), dim3(256), 0, (hipStream_t)stream, x, w, bias,
                      out, flag, N, H, W);

@@ -1582,6 +1582,9 @@ static int conv_build(const float* const* src, int n_src, int cin_per_src, const
   // Map the requested fusion onto a compiled epilogue (relu -> mask -> +res0 -> +res1).
   if (mode == 1) {
     if (relu || mask || res0 || res1) return (int)hipErrorInvalidValue;
+    // (the pixel-shuffle epilogue of EVERY staging path moves a lane's four HR pixels as one 16-byte access: the HR
+    // output and the base image have no narrower walk)
+    if ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(base)) & 15) return (int)hipErrorInvalidValue;
     epi = base ? kEpiShuffleBase : kEpiShuffle;
   } else {
     if (base) return (int)hipErrorInvalidValue;
@@ -1734,11 +1737,13 @@ int larva_conv3x3_exit_l1_batch(int njobs, const float* const* src, int n_src, i
     bool aligned;
     int epi;
     if (!base[j] || !truth[j] || !grad[j] || !partial[j]) return (int)hipErrorInvalidValue;
+    if ((reinterpret_cast<uintptr_t>(truth[j]) | reinterpret_cast<uintptr_t>(base[j]) | reinterpret_cast<uintptr_t>(grad[j]) |
+         reinterpret_cast<uintptr_t>(out[j])) & 15)
+      return (int)hipErrorNotSupported;
     const int rc = conv_build(src + (size_t)j * n_src, n_src, cin_per_src, wpk[j], bias ? bias[j] : nullptr, nullptr,
                               nullptr, nullptr, base[j], grad[j], N, H, W, pitch, 0, 1, b.job[j], aligned, epi);
     if (rc) return rc;
-    if (!aligned || ((reinterpret_cast<uintptr_t>(truth[j]) | reinterpret_cast<uintptr_t>(base[j])) & 15))
-      return (int)hipErrorNotSupported;
+    if (!aligned) return (int)hipErrorNotSupported;
     b.job[j].out = out[j];
     b.job[j].truth = truth[j];
     b.job[j].grad = grad[j];

@@ -17,7 +17,9 @@ __device__ __forceinline__ void cubic_coeffs(float t, float (&w)[4]) {
 }
 
 // One thread produces the 4 horizontally adjacent outputs of one LR pixel in one HR row; work item i of
-// planes * 4H * W, `first` / `stride` = this thread's grid-stride walk.
+// planes * 4H * W, `first` / `stride` = this thread's grid-stride walk.  VEC: `out` is 16-byte aligned and the four
+// floats leave as one store; otherwise as four (the same values).
+template <bool VEC = true>
 __device__ __forceinline__ void bicubic4_body(const float* __restrict__ in, float* __restrict__ out, int planes,
                                               int H, int W, long long first, long long stride) {
   const int HH = 4 * H;
@@ -61,7 +63,13 @@ __device__ __forceinline__ void bicubic4_body(const float* __restrict__ in, floa
       }
       o[jj] = acc;
     }
-    *reinterpret_cast<f32x4*>(out + ((size_t)p * HH + Y) * (4 * W) + 4 * x) = o;
+    float* dst = out + ((size_t)p * HH + Y) * (4 * W) + 4 * x;
+    if constexpr (VEC) {
+      *reinterpret_cast<f32x4*>(dst) = o;
+    } else {
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) dst[jj] = o[jj];
+    }
   }
 }
 

@@ -13,10 +13,11 @@ namespace larva {
 // A = -0.75; row pass first, then the column weights (the order of ATen's separable CPU path).
 // One thread produces the 4 horizontally adjacent outputs of one LR pixel in one HR row.
 // ---------------------------------------------------------------------------------------------
+template <bool VEC>
 __global__ void bicubic4_kernel(const float* __restrict__ in, float* __restrict__ out, int planes,
                                 int H, int W) {
-  bicubic4_body(in, out, planes, H, W, (long long)blockIdx.x * blockDim.x + threadIdx.x,
-                (long long)gridDim.x * blockDim.x);
+  bicubic4_body<VEC>(in, out, planes, H, W, (long long)blockIdx.x * blockDim.x + threadIdx.x,
+                     (long long)gridDim.x * blockDim.x);
 }
 
 // The same arithmetic, one thread per LR pixel = its 4 x 4 block of HR pixels (the stand-alone launch of the inference
@@ -709,14 +710,17 @@ extern "C" {
 int larva_bicubic4_fwd(const float* in, float* out, int N, int C, int H, int W, void* stream) {
   if (!in || !out || N <= 0 || C <= 0 || H <= 0 || W <= 0) return (int)hipErrorInvalidValue;
   const long long px = (long long)N * C * H * W;
-  if (px < (1ll << 31) - 256 && !(reinterpret_cast<uintptr_t>(out) & 15)) {   // one thread per LR pixel = a 4 x 4 block of HR pixels
+  const bool vec = !(reinterpret_cast<uintptr_t>(out) & 15);
+  if (px < (1ll << 31) - 256 && vec) {   // one thread per LR pixel = a 4 x 4 block of HR pixels
     hipLaunchKernelGGL(bicubic4_block_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in, out,
                        (unsigned)(N * C), (unsigned)H, (unsigned)W);
     return (int)hipGetLastError();
   }
   const long long work = (long long)N * C * 4 * H * W;
-  hipLaunchKernelGGL(bicubic4_kernel, dim3(grid_for(work, 256)), dim3(256), 0, (hipStream_t)stream, in, out,
-                     N * C, H, W);
+  // (an `out` that is only 4-byte aligned: the same arithmetic, four 4-byte stores per lane instead of one 16-byte store)
+  const dim3 grid(grid_for(work, 256)), block(256);
+  if (vec) hipLaunchKernelGGL(bicubic4_kernel<true>, grid, block, 0, (hipStream_t)stream, in, out, N * C, H, W);
+  else hipLaunchKernelGGL(bicubic4_kernel<false>, grid, block, 0, (hipStream_t)stream, in, out, N * C, H, W);
   return (int)hipGetLastError();
 }
 
@@ -916,6 +920,7 @@ int larva_l1_bwd(const float* a, const float* b, const float* gout, long long nu
 // in [N][C][4H][4W] -> out [N][16C][H][W]
 int larva_pixel_unshuffle4(const float* in, float* out, int N, int C, int H, int W, void* stream) {
   if (!in || !out || N <= 0 || C <= 0 || H <= 0 || W <= 0) return (int)hipErrorInvalidValue;
+  if (reinterpret_cast<uintptr_t>(in) & 15) return (int)hipErrorInvalidValue;   // (16-byte loads of `in`)
   const long long work = (long long)N * C * 4 * H * W;
   hipLaunchKernelGGL(pixel_unshuffle4_kernel, dim3(grid_for(work, 256)), dim3(256), 0, (hipStream_t)stream, in,
                      out, N * C, H, W);

@@ -1282,10 +1282,11 @@ static int wgrad_flat_impl(const float* const* dy, const float* const* x, float*
     return (int)hipErrorNotSupported;
   const bool head = head_dy || head_x16 || head_partial;
   if (head && cout != 48) return (int)hipErrorNotSupported;   // (the head's tail role is priced for the 48-channel grid)
-  if (head && (!head_dy || !head_x16 || !head_partial || !head_splits_out)) return (int)hipErrorInvalidValue;
+  if (head && (!head_dy || !head_x16 || !head_partial || !head_splits_out || (reinterpret_cast<uintptr_t>(head_partial) & 15)))
+    return (int)hipErrorInvalidValue;
   WgradBatch b{};
   for (int i = 0; i < njobs; ++i) {
-    if (!dy[i] || !x[i] || !partial[i]) return (int)hipErrorInvalidValue;
+    if (!dy[i] || !x[i] || !partial[i] || (reinterpret_cast<uintptr_t>(partial[i]) & 15)) return (int)hipErrorInvalidValue;
     if ((reinterpret_cast<uintptr_t>(dy[i]) | reinterpret_cast<uintptr_t>(x[i])) & 15) return (int)hipErrorNotSupported;
     b.job[i] = WgradJob{dy[i], x[i], partial[i]};
   }
@@ -1408,7 +1409,8 @@ int larva_conv3x3_wgrad_partial(const float* const* dy, const float* const* x, f
   WgradBatch b{};
   bool aligned = (W % 4 == 0);
   for (int i = 0; i < njobs; ++i) {
-    if (!dy[i] || !x[i] || !partial[i]) return (int)hipErrorInvalidValue;
+    // (partial images are written, and read back by the reduction, 16 bytes per lane on every path)
+    if (!dy[i] || !x[i] || !partial[i] || (reinterpret_cast<uintptr_t>(partial[i]) & 15)) return (int)hipErrorInvalidValue;
     b.job[i] = WgradJob{dy[i], x[i], partial[i]};
     aligned = aligned && ((reinterpret_cast<uintptr_t>(dy[i]) & 15) == 0) &&
               ((reinterpret_cast<uintptr_t>(x[i]) & 15) == 0);
@@ -1451,7 +1453,8 @@ static int reduce_launch(const float* const* partial, float* const* dw, float* c
   ReduceBatch rb{};
   int pf_max = 0;
   for (int i = 0; i < njobs; ++i) {
-    if (!partial[i] || !dw[i] || splits[i] < 1 || cout[i] <= 0 || cin[i] <= 0 || cout[i] % 16 || cin[i] % 16)
+    if (!partial[i] || (reinterpret_cast<uintptr_t>(partial[i]) & 15) || !dw[i] || splits[i] < 1 || cout[i] <= 0 ||
+        cin[i] <= 0 || cout[i] % 16 || cin[i] % 16)
       return (int)hipErrorInvalidValue;
     rb.job[i] = ReduceJob{partial[i], dw[i], db ? db[i] : nullptr, cin_off[i], cin_valid[i], w_cin_total[i],
                           splits[i], cout[i], cin[i]};

@@ -163,7 +163,10 @@ def conv3x3(srcs, wpk, cout, bias=None, relu=False, mask=None, res0=None, res1=N
     the strip launch writes its output with plain instead of non-temporal stores.
     tile_rows: 0 = the library picks the tiling of a whole-tensor launch (3 x 48 tiles; 4 x 48 for large 32-channel
     launches; persistent workgroups where there are more tiles than workgroup slots), 3 / 4 = that tile height (tests,
-    A/B timing; larva_conv3x3_fwd_tiled)."""
+    A/B timing; larva_conv3x3_fwd_tiled).
+    Views: srcs, wpk, mask, res0, res1 and a shuffle=False out may start on any 4-byte boundary (off the 16-byte grid the
+    register-staged kernel runs: same results; strips then fall back to the regular tiles, tile_rows=4 raises); with
+    shuffle=True `out` and `base` must be 16-byte aligned (RuntimeError otherwise, nothing is written)."""
     lib = hip_lib.load()
     if isinstance(srcs, torch.Tensor):
         srcs = [srcs]
