@@ -503,6 +503,27 @@ int larva_rgb_u8_to_i420(const unsigned char* img, unsigned char* out, long long
 int larva_resize_u8(const unsigned char* src, unsigned char* dst, int N, int H, int W, int h, int w, const int* hbounds,
                     const int* hcoeffs, int kx, const int* vbounds, const int* vcoeffs, int ky, void* stream);
 
+/* ---- transparency: straight-alpha RGBA images (csrc/larva_rgba.hip) --------------------------------------
+ * An RGBA batch runs through the RGB forward as N + K batch slots: slot n is image n's colour, and an image that is not
+ * opaque owns one more slot, alpha_slot[n] in [N, N + K), that carries its alpha plane as a grey image.  alpha_slot is a
+ * DEVICE int32 [N] (image_utils.alpha_slots makes it; K <= N); an entry outside [N, N + K) -- -1 by convention -- marks an
+ * opaque image, so no entry can send an access outside the tensors.  image_utils.rgba_split_f32 / rgba_merge_u8 are the
+ * definition and both launches equal them bit for bit.
+ *
+ * larva_rgba_u8_split_f32: rgba uint8 [N][H][W][4] -> out fp32 [N + K][3][H][W], exact: out[n][c] = channel c of image
+ * n, out[alpha_slot[n]][0..2] = its alpha.  Slots no image names are not written.
+ * larva_rgb_u8_merge_rgba: rgb uint8 [N + K][h][w][3] -> out uint8 [N][h][w][4]: channels 0..2 from slot n, channel 3 =
+ * (r + g + b + 1) / 3 of slot alpha_slot[n] in integers, 255 for an opaque image.
+ *
+ * One launch each, any N, H, W >= 1.  Where H W is a multiple of 4 and the pointers are aligned (RGBA images and fp32
+ * planes to 16 bytes, RGB images to 4) a lane moves 4 pixels with 16-byte accesses to the RGBA image and the planes;
+ * otherwise one pixel per lane, the RGBA pixel as one word where that image is 4-byte aligned, else as bytes.  The values
+ * do not depend on the path.  hipErrorInvalidValue before the launch for a NULL pointer or a bad shape. */
+int larva_rgba_u8_split_f32(const unsigned char* rgba, const int* alpha_slot, float* out, int N, int K, int H, int W,
+                            void* stream);
+int larva_rgb_u8_merge_rgba(const unsigned char* rgb, const int* alpha_slot, unsigned char* out, int N, int K, int h, int w,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,8 @@ import sys
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "liblarva_hip.so")
 SOURCES = ["conv3x3_mfma.hip", "wgrad3x3_mfma.hip", "larva_pointwise.hip", "larva_scale.hip", "conv3x3_f16.hip",
-           "larva_metrics.hip", "larva_ensemble.hip", "larva_downscale.hip", "larva_yuv.hip", "larva_resize.hip"]
+           "larva_metrics.hip", "larva_ensemble.hip", "larva_downscale.hip", "larva_yuv.hip", "larva_resize.hip",
+           "larva_rgba.hip"]
 HEADERS = ["larva_common.h", "larva_bicubic.h", "larva_loss.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

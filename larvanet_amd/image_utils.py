@@ -176,6 +176,68 @@ def resize_u8(image, out_h, out_w):
     return np.ascontiguousarray(a)
 
 
+# ------------------------------------------------------------------ transparency: straight-alpha RGBA images
+# An RGBA image keeps its alpha by running it through the network too: the colour is what upscale_u8 returns for the RGB
+# part, and the alpha plane, repeated into a grey image, takes the same forward; its three result channels are merged as
+# (r + g + b + 1) // 3, the nearest integer to their mean (a third has no ties), in int32.  An opaque image (alpha 255
+# everywhere) keeps alpha 255 and runs no alpha forward: the network does not map flat 255 to flat 255.  Alpha is straight
+# (not premultiplied); the colour under transparent pixels is used as it is.  A batch of N images, K of them not opaque,
+# is N + K batch slots of the RGB forward: slot n = image n's colour, slot alpha_slot[n] >= N = its alpha.  These three
+# functions are the definition; kernels.rgba_u8_split_f32 / rgb_u8_merge_rgba (csrc/larva_rgba.hip) equal them bit for bit.
+def alpha_slots(opaque):
+    """N opacity flags -> (int32 [N] table, K): -1 for an opaque image, else its alpha slot; the K slots N .. N + K - 1 are
+    handed out in image order."""
+    flags = [bool(f) for f in opaque]
+    table = np.full(len(flags), -1, np.int32)
+    k = 0
+    for n, f in enumerate(flags):
+        if not f:
+            table[n] = len(flags) + k
+            k += 1
+    return table, k
+
+
+def _check_alpha_slots(alpha_slot, n):
+    """-> (int table, K); ValueError unless the entries >= 0 are the slots n .. n + K - 1, each once."""
+    table = [int(s) for s in np.asarray(alpha_slot).reshape(-1)]
+    used = sorted(s for s in table if s >= 0)
+    if len(table) != n or any(s < -1 for s in table) or used != list(range(n, n + len(used))):
+        raise ValueError("larvanet_amd: alpha_slot must hold %d entries, -1 or the slots %d .. %d + K - 1 each once, got %s"
+                         % (n, n, n, table))
+    return table, len(used)
+
+
+def rgba_split_f32(images_u8, alpha_slot):
+    """uint8 (N, H, W, 4) -> float32 (N + K, 3, H, W), exact: slot n holds image n's colour planes, slot alpha_slot[n] >= N
+    its alpha plane three times; alpha_slot[n] == -1 (an opaque image) has no alpha slot."""
+    a = np.asarray(images_u8)
+    if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 4 or min(a.shape) < 1:
+        raise ValueError("larvanet_amd: rgba_split_f32 takes a uint8 (N, H, W, 4) batch, got %s %s" % (a.dtype, a.shape,))
+    n = a.shape[0]
+    table, k = _check_alpha_slots(alpha_slot, n)
+    out = np.empty((n + k, 3) + a.shape[1:3], np.float32)
+    out[:n] = a[..., :3].transpose(0, 3, 1, 2)
+    for i, s in enumerate(table):
+        if s >= 0:
+            out[s] = a[i, :, :, 3][None]
+    return out
+
+
+def rgba_merge_u8(rgb_u8, alpha_slot, n):
+    """uint8 (N + K, h, w, 3) (the forward's result for rgba_split_f32's slots) -> uint8 (N, h, w, 4): channels 0..2 from
+    slot n, channel 3 = (r + g + b + 1) // 3 of slot alpha_slot[n] in int32, 255 where alpha_slot[n] == -1."""
+    a = np.asarray(rgb_u8)
+    n = int(n)
+    table, k = _check_alpha_slots(alpha_slot, n)
+    if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 3 or a.shape[0] != n + k or min(a.shape) < 1:
+        raise ValueError("larvanet_amd: rgba_merge_u8 takes a uint8 (%d, h, w, 3) batch, got %s %s" % (n + k, a.dtype, a.shape,))
+    out = np.empty((n,) + a.shape[1:3] + (4,), np.uint8)
+    out[..., :3] = a[:n]
+    for i, s in enumerate(table):
+        out[i, :, :, 3] = 255 if s < 0 else (a[s].astype(np.int32).sum(axis=2) + 1) // 3
+    return out
+
+
 # ------------------------------------------------------------------ planar YUV 4:2:0 (I420) <-> RGB, in exact integers
 # A frame is ONE contiguous uint8 buffer: Y [H][W], then U [ch][cw], then V [ch][cw], cw = (W + 1) // 2, ch = (H + 1) // 2.
 # Odd W and H are legal; a coordinate outside a plane is the edge's (clamped), reading and writing.  Chroma is centred on

@@ -1432,3 +1432,73 @@ def resize_u8(x_u8_hwc, out_h, out_w, out=None):
     hip_lib.check(lib.larva_resize_u8(x.data_ptr(), out.data_ptr(), N, H, W, h, w, ptr(hb), ptr(hc), kx, ptr(vb), ptr(vc), ky,
                                       _stream()), "larva_resize_u8")
     return out
+
+
+# ------------------------------------------------------------------ transparency: RGBA images (csrc/larva_rgba.hip)
+_ALPHA_TABLES = {}       # (opacity flags, device) -> (int32 [N] device table, K); a handful of entries per folder
+_ALPHA_TABLES_MAX = 64
+
+
+def alpha_slot_table(opaque, device):
+    """image_utils.alpha_slots(opaque) with the table on `device`, cached -> (int32 [N] device tensor, K)."""
+    key = (tuple(bool(f) for f in opaque), str(device))
+    hit = _ALPHA_TABLES.get(key)
+    if hit is None:
+        from .image_utils import alpha_slots
+        table, k = alpha_slots(key[0])
+        while len(_ALPHA_TABLES) >= _ALPHA_TABLES_MAX:
+            _ALPHA_TABLES.pop(next(iter(_ALPHA_TABLES)))
+        hit = (torch.from_numpy(table).to(device), k)
+        _ALPHA_TABLES[key] = hit
+    return hit
+
+
+def _chk_alpha_slot(alpha_slot, n, k, device):
+    _chk_tensor(alpha_slot, "alpha_slot", (n,), torch.int32)
+    if alpha_slot.device != device:
+        raise RuntimeError("larvanet_amd: alpha_slot must be on the images' device")
+    k = int(k)
+    if not 0 <= k <= n:
+        raise RuntimeError("larvanet_amd: K (the alpha slots) must be 0 .. N = %d, got %d" % (n, k))
+    return k
+
+
+def rgba_u8_split_f32(x, alpha_slot, k, out=None):
+    """uint8 [N][H][W][4] RGBA -> float32 [N + K][3][H][W], exact, in one launch (image_utils.rgba_split_f32): slot n = the
+    colour planes of image n, slot alpha_slot[n] = its alpha three times.  alpha_slot: int32 [N] on the device
+    (alpha_slot_table), K of its entries name the slots N .. N + K - 1, every other entry means opaque."""
+    lib = hip_lib.load()
+    _chk_tensor(x, "x", None, torch.uint8, 4)
+    N, H, W = (int(v) for v in x.shape[:3])
+    if min(N, H, W) < 1:
+        raise RuntimeError("larvanet_amd: x must not be empty, got %s" % (tuple(x.shape),))
+    k = _chk_alpha_slot(alpha_slot, N, k, x.device)
+    if out is None:
+        out = torch.empty((N + k, 3, H, W), device=x.device, dtype=torch.float32)
+    _chk(out, "out", (N + k, 3, H, W))
+    if out.device != x.device:
+        raise RuntimeError("larvanet_amd: x and out must be on one device")
+    hip_lib.check(lib.larva_rgba_u8_split_f32(x.data_ptr(), alpha_slot.data_ptr(), out.data_ptr(), N, k, H, W, _stream()),
+                  "larva_rgba_u8_split_f32")
+    return out
+
+
+def rgb_u8_merge_rgba(rgb, alpha_slot, n, out=None):
+    """uint8 [N + K][h][w][3] (the forward's result for rgba_u8_split_f32's slots) -> uint8 [N][h][w][4] in one launch
+    (image_utils.rgba_merge_u8): colour from slot n, alpha = (r + g + b + 1) // 3 of slot alpha_slot[n], 255 for an image
+    without a slot.  out: a contiguous uint8 [N][h][w][4] tensor to fill."""
+    lib = hip_lib.load()
+    _chk_u8(rgb, "rgb")
+    n = int(n)
+    M, h, w = (int(v) for v in rgb.shape[:3])
+    if n < 1 or min(h, w) < 1 or not n <= M <= 2 * n:
+        raise RuntimeError("larvanet_amd: rgb must hold N + K slots (N = %d, 0 <= K <= N), got %s" % (n, tuple(rgb.shape)))
+    k = _chk_alpha_slot(alpha_slot, n, M - n, rgb.device)
+    if out is None:
+        out = torch.empty((n, h, w, 4), device=rgb.device, dtype=torch.uint8)
+    _chk_tensor(out, "out", (n, h, w, 4), torch.uint8, 4)
+    if out.device != rgb.device:
+        raise RuntimeError("larvanet_amd: rgb and out must be on one device")
+    hip_lib.check(lib.larva_rgb_u8_merge_rgba(rgb.data_ptr(), alpha_slot.data_ptr(), out.data_ptr(), n, k, h, w, _stream()),
+                  "larva_rgb_u8_merge_rgba")
+    return out

@@ -958,7 +958,7 @@ class LarvaNet(BaseModel):
         h, w = (int(v) for v in (x.shape[1:3] if x.dtype == torch.uint8 else x.shape[2:4]))
         half = self._half()
         run = half if half is not None else self.model
-        with HeadFn.rule_batch_as(n):
+        with HeadFn.rule_batch_as(HeadFn.rule_batch or n):   # (a caller that runs slots of its own has named its images)
             if h == w:
                 both = torch.empty((8 * n, 3, h, w), device=x.device, dtype=torch.float32)
                 K.dihedral_inputs(x, out=(both[:4 * n], both[4 * n:]))
@@ -1125,6 +1125,74 @@ class LarvaNet(BaseModel):
             out = self._infer_checked(x, u8=True)
             records = torch.stack([K.u8_metrics(out[n], truth[n], shave, channel, ssim) for n in range(out.shape[0])])
         return [K.metrics_from_record(r) for r in records.cpu().numpy()]
+
+    # ------------------------------------------------------------------ transparency: RGBA images in and out
+    def _check_rgba_images(self, input_list, scale):
+        """Host-side argument checks of upscale_rgba_u8 (before any device work) -> the (N, H, W, 4) uint8 batch."""
+        if int(scale) != self.scale:
+            raise ValueError("larvanet_amd: this model upscales by %d, not by %r" % (self.scale, scale))
+        if isinstance(input_list, np.ndarray) or not len(input_list):
+            raise ValueError("larvanet_amd: upscale_rgba_u8 takes a non-empty list of (H, W, 4) uint8 arrays")
+        for a in input_list:
+            if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
+                raise TypeError("larvanet_amd: upscale_rgba_u8 takes uint8 numpy arrays (decoded images), got %s"
+                                % (getattr(a, "dtype", type(a).__name__),))
+            if a.ndim != 3 or a.shape[2] != 4 or a.shape[0] < 1 or a.shape[1] < 1:
+                raise ValueError("larvanet_amd: upscale_rgba_u8 takes (H, W, 4) images, got shape %s" % (a.shape,))
+            if a.shape != input_list[0].shape:
+                raise ValueError("larvanet_amd: the images of one upscale_rgba_u8 call must have one shape, got %s and %s"
+                                 % (input_list[0].shape, a.shape))
+        return np.ascontiguousarray(np.stack(input_list))
+
+    def _infer_rgba(self, x_u8, opaque, infer, out=None):
+        """uint8 [N][H][W][4] on the device -> uint8 [N][h][w][4]: one launch splits the batch into the float planes of
+        N + K slots (image n's colour in slot n, the alpha plane of each of the K images that are not known to be opaque as
+        a grey image of its own), infer(planes) -- the uint8 forward that takes float planes, as the video path's --
+        returns the uint8 [N + K][h][w][3] result, and one launch merges it (alpha = the rounded mean of its slot's three
+        channels, 255 for an opaque image) into `out` or a new tensor.  Both launches sit outside the forward's graph.  A
+        pixel's result does not depend on its batch slot, and the head kernel is chosen as the RGB call of these N images
+        would choose it, so the colour is upscale_u8's bit for bit."""
+        n = int(x_u8.shape[0])
+        slot, k = K.alpha_slot_table(opaque, x_u8.device)
+        planes = K.rgba_u8_split_f32(x_u8, slot, k)
+        with HeadFn.rule_batch_as(n):
+            rgb = infer(planes)
+        return K.rgb_u8_merge_rgba(rgb, slot, n, out=out)
+
+    def upscale_rgba_u8(self, input_list, scale, output_size=None):
+        """list of uint8 (H, W, 4) straight-alpha RGBA images of one shape -> uint8 (N, sH, sW, 4) numpy.  Channels 0..2 are
+        upscale_u8 of the RGB part byte for byte; the alpha goes through the same network as a grey image and its three
+        result channels are merged as (r + g + b + 1) // 3 (image_utils.rgba_merge_u8).  An opaque image (alpha 255
+        everywhere, decided here on the host) keeps alpha 255 and costs what its RGB part costs.  output_size = (height,
+        width): colour and alpha each go through image_utils.resize_u8 before the merge -> (N, height, width, 4)."""
+        batch = self._check_rgba_images(input_list, scale)
+        size = self._output_size(output_size, batch.shape[1], batch.shape[2])
+        opaque = [bool(a[..., 3].min() == 255) for a in batch]
+        with torch.no_grad():
+            x = torch.from_numpy(batch).to(self.device)
+            _require_hip(x)
+            return self._infer_rgba(x, opaque, lambda planes: self._infer_sized(planes, size)).cpu().numpy()
+
+    def upscale_rgba_u8_tensor(self, x_u8, opaque=None, output_size=None):
+        """upscale_rgba_u8 without the trips to and from the host: uint8 [N][H][W][4] on self.device -> uint8
+        [N][sH][sW][4], or [N][height][width][4] with output_size.  opaque: None (no image is known to be opaque: every
+        alpha plane runs through the network) or N bools; the tensor is never read back to find out."""
+        if not isinstance(x_u8, torch.Tensor) or x_u8.dtype != torch.uint8:
+            raise TypeError("larvanet_amd: upscale_rgba_u8_tensor takes a uint8 tensor, got %s"
+                            % (getattr(x_u8, "dtype", type(x_u8).__name__),))
+        if x_u8.dim() != 4 or x_u8.shape[3] != 4 or min(x_u8.shape) < 1:
+            raise ValueError("larvanet_amd: upscale_rgba_u8_tensor takes [N][H][W][4], got shape %s" % (tuple(x_u8.shape),))
+        n = int(x_u8.shape[0])
+        if opaque is None:
+            opaque = [False] * n
+        else:
+            opaque = list(opaque)
+            if len(opaque) != n or not all(isinstance(f, (bool, np.bool_)) for f in opaque):
+                raise ValueError("larvanet_amd: opaque must be None or %d bools (one per image), got %r" % (n, opaque))
+        size = self._output_size(output_size, x_u8.shape[1], x_u8.shape[2])
+        _require_hip(x_u8)
+        with torch.no_grad():
+            return self._infer_rgba(x_u8.contiguous(), opaque, lambda planes: self._infer_sized(planes, size))
 
     # ------------------------------------------------------------------ video: planar YUV 4:2:0 frames in and out
     def _check_yuv_args(self, width, height, matrix, full_range, scale=None):

@@ -27,6 +27,11 @@ stream around the forward, the second one writing straight into the slot's outpu
 With output_size = (height, width) both upscaling streams resize every result to that one size on the device
 (kernels.resize_u8, one eager launch on the compute stream behind the forward; for video between the forward's uint8 RGB
 image and rgb_u8_to_i420): the slot's output buffers, and what crosses the host link on the way back, have the target size.
+
+With keep_alpha upscale_stream also takes (H, W, 4) straight-alpha RGBA images, freely mixed with RGB ones: one launch
+splits an RGBA image into the float planes of its colour and (unless it is opaque) of its alpha as a second batch slot, the
+forward runs them together, and one launch merges the result into the slot's 4-channel output buffer
+(kernels.rgba_u8_split_f32 / rgb_u8_merge_rgba); 4 bytes per pixel cross the host link each way.
 """
 import collections
 
@@ -93,12 +98,15 @@ class _Slot:
         return self.pin_out[:n].view(shape), self.dev_out[:n].view(shape)
 
 
-def _check_image(a, who="upscale_stream"):
+def _check_image(a, who="upscale_stream", keep_alpha=False):
     if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
         raise TypeError("larvanet_amd: %s takes uint8 numpy arrays (decoded images), got %s"
                         % (who, getattr(a, "dtype", type(a).__name__),))
+    if keep_alpha and a.ndim == 3 and a.shape[2] == 4 and a.shape[0] >= 1 and a.shape[1] >= 1:
+        return
     if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
-        raise ValueError("larvanet_amd: %s takes (H, W, 3) images, got shape %s" % (who, a.shape,))
+        raise ValueError("larvanet_amd: %s takes (H, W, 3) images%s, got shape %s"
+                         % (who, " and, with keep_alpha, (H, W, 4) ones" if keep_alpha else "", a.shape,))
 
 
 def _check_target(output_size):
@@ -107,9 +115,11 @@ def _check_target(output_size):
     return None if output_size is None else check_output_size(output_size, 1, 1)
 
 
-def upscale_stream(model, images, scale, depth=2, output_size=None):
+def upscale_stream(model, images, scale, depth=2, output_size=None, keep_alpha=False):
     """Generator: uint8 (H, W, 3) numpy images of any sizes -> their uint8 (sH, sW, 3) upscaled images, in input order;
     each result equals model.upscale_u8([image], scale)[0].  At most `depth` images are in flight (depth 1 = no overlap).
+    keep_alpha=True: (H, W, 4) RGBA images are taken too, in any mix with RGB ones, and come back with 4 channels, each
+    equal to model.upscale_rgba_u8([image], scale)[0]; the default refuses them as before.
     output_size = (height, width): every result is resized to it on the device and equals model.upscale_u8([image], scale,
     output_size=output_size)[0]; an image the size is out of range for raises ValueError before anything of it is launched.
     Under --precision fp16 an image whose activations overflow raises FloatingPointError when its turn to be yielded
@@ -123,7 +133,7 @@ def upscale_stream(model, images, scale, depth=2, output_size=None):
         raise ValueError("larvanet_amd: this model upscales by %d, not by %r" % (model.scale, scale))
     if model.device.type != "cuda":
         raise RuntimeError("larvanet_amd: upscale_stream only runs on a HIP device (MI355X); there is no CPU fallback")
-    return _stream(model, images, depth, target=target)
+    return _stream(model, images, depth, target=target, keep_alpha=bool(keep_alpha))
 
 
 def evaluate_stream(model, pairs, scale, shave=None, channel="y", ssim=True, depth=2, keep_images=False):
@@ -186,11 +196,11 @@ def upscale_yuv_stream(model, frames, scale, width=None, height=None, matrix="bt
     return _stream(model, frames, depth, yuv={"size": size, "matrix": matrix, "full_range": bool(full_range)}, target=target)
 
 
-def _stream(model, images, depth, score=None, yuv=None, target=None):
+def _stream(model, images, depth, score=None, yuv=None, target=None, keep_alpha=False):
     """The pipeline of upscale_stream; with `score` (evaluate_stream's settings) the items are (input, truth) pairs; with
     `yuv` (upscale_yuv_stream's settings) they are I420 frames, or (frame, width, height) triples; with `target` = (height,
-    width) the two upscaling streams resize every result to it."""
-    if score is not None or yuv is not None or target is not None:
+    width) the two upscaling streams resize every result to it; with keep_alpha upscale_stream takes RGBA images too."""
+    if score is not None or yuv is not None or target is not None or keep_alpha:
         from . import kernels as K
     if yuv is not None:
         from .image_utils import i420_frame_bytes
@@ -243,7 +253,7 @@ def _stream(model, images, depth, score=None, yuv=None, target=None):
                     model._output_size(target, fh, fw)
                     image = image[None]   # (a batch of one frame: [1][frame bytes])
                 elif score is None:
-                    _check_image(image)
+                    _check_image(image, keep_alpha=keep_alpha)
                     model._output_size(target, image.shape[0], image.shape[1])
                 else:
                     image, truth = image
@@ -286,6 +296,12 @@ def _stream(model, images, depth, score=None, yuv=None, target=None):
                         out = K.resize_u8(out, target[0], target[1])
                     slot.out_shape = (1, 1, i420_frame_bytes(out.shape[2], out.shape[1]))
                     K.rgb_u8_to_i420(out, yuv["matrix"], yuv["full_range"], out=slot.views_out(slot.out_shape)[1][0])
+                elif dev_in.shape[3] == 4:   # RGBA: split -> forward over colour (and alpha) -> merged into the slot's buffer
+                    def infer(planes):
+                        out = model._infer_u8_images(planes)
+                        return out if target is None else K.resize_u8(out, target[0], target[1])
+                    slot.out_shape = (1,) + (target or tuple(model.scale * v for v in image.shape[:2])) + (4,)
+                    model._infer_rgba(dev_in, [bool(image[..., 3].min() == 255)], infer, out=slot.views_out(slot.out_shape)[1])
                 else:
                     out = model._infer_u8_images(dev_in)   # (the x8 self-ensemble under --self_ensemble)
                     if target is not None:   # (upscale_stream only: resized straight into the slot's own buffer)

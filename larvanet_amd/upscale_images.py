@@ -3,11 +3,17 @@ is written as <output_path>/<stem>.png.
 
     python -m larvanet_amd.upscale_images --model=LarvaNet --num_modules=4 --num_blocks=4,4,4,4 \\
         --restore_path=model.pth --input_path=LR --output_path=SR [--precision fp16] [--self_ensemble]
-        [--io_threads 8] [--all_exits] [--output_size 1920x1080]
+        [--io_threads 8] [--all_exits] [--output_size 1920x1080] [--keep_alpha]
 
 --output_size WxH writes every image at exactly that size instead of the network's integer multiple: the upscaled image is
 resized on the device before it leaves it (Pillow's bicubic, byte for byte: image_utils.resize_u8).  An axis may shrink
 by at most 4 from the network's output; the PNG headers are checked against that before any image is decoded.
+
+--keep_alpha keeps transparency: a file whose mode carries alpha (RGBA, LA, PA, or P / RGB / L with a transparency entry)
+is decoded as straight-alpha RGBA, its alpha plane goes through the network beside the colour (as a grey image, merged on
+the device: model.upscale_rgba_u8) and it is written as an RGBA PNG; an image whose alpha is 255 everywhere costs what an
+RGB image costs.  Every other file goes the RGB way.  Without the flag alpha is dropped, as before.  The colour under
+fully transparent pixels is used as it is: garbage there rings into visible neighbours.  Not together with --all_exits.
 
 --all_exits writes every exit of the multi-exit network from ONE forward pass per image, as <stem>_exit<k>.png with k
 counted from 1 like --leg (model.upscale_exits_u8): the head and the bodies run once, the legs go out together.  It runs
@@ -53,7 +59,16 @@ def build_parser():
     p.add_argument("--output_size", type=str, default=None,
                    help="WIDTHxHEIGHT of the written images (e.g. 1920x1080): the upscaled image is resized on the device "
                         "(bicubic, Pillow's bytes); default: scale times the input size")
+    p.add_argument("--keep_alpha", action="store_true",
+                   help="files with an alpha channel or a transparency entry are upscaled and written as RGBA (the alpha "
+                        "plane goes through the network too); default: alpha is dropped")
     return p
+
+
+def check_keep_alpha(args):
+    """ValueError for --keep_alpha together with --all_exits (there is no all-exit RGBA)."""
+    if args.keep_alpha and args.all_exits:
+        raise ValueError("larvanet_amd.upscale_images: --keep_alpha together with --all_exits is not supported")
 
 
 def output_size_of(args):
@@ -106,7 +121,21 @@ def read_rgb(path):
         return np.ascontiguousarray(np.asarray(im.convert("RGB"), dtype=np.uint8))
 
 
+def carries_alpha(im):
+    """Does this opened PIL image carry transparency: an alpha band (RGBA, LA, PA) or a `transparency` entry (P, RGB, L)?"""
+    return im.mode in ("RGBA", "LA", "PA") or "transparency" in im.info
+
+
+def read_image(path, keep_alpha=False):
+    """read_rgb; with keep_alpha a file that carries transparency is decoded as (H, W, 4) straight-alpha RGBA instead."""
+    from PIL import Image
+    with Image.open(path) as im:
+        mode = "RGBA" if keep_alpha and carries_alpha(im) else "RGB"
+        return np.ascontiguousarray(np.asarray(im.convert(mode), dtype=np.uint8))
+
+
 def write_rgb(image_hwc_uint8, path):
+    """(H, W, 3) -> an RGB PNG, (H, W, 4) -> an RGBA PNG."""
     from PIL import Image
     Image.fromarray(image_hwc_uint8).save(path)
 
@@ -124,6 +153,7 @@ def _prefetched(pool, fn, items, ahead):
 
 def main(argv=None):
     args, remaining = build_parser().parse_known_args(argv)
+    check_keep_alpha(args)
     target = output_size_of(args)
     if args.cuda_device is not None and "LOCAL_RANK" not in os.environ:
         os.environ["HIP_VISIBLE_DEVICES"] = args.cuda_device
@@ -177,9 +207,11 @@ def main(argv=None):
         print("- average duration: %.4fs" % np.mean(list(durations.values())))
         return durations
     with concurrent.futures.ThreadPoolExecutor(max_workers=threads) as pool:
-        decoded = _prefetched(pool, read_rgb, [os.path.join(args.input_path, n) for n in mine], ahead=threads + args.depth)
+        read = (lambda path: read_image(path, True)) if args.keep_alpha else read_rgb
+        decoded = _prefetched(pool, read, [os.path.join(args.input_path, n) for n in mine], ahead=threads + args.depth)
         last = time.perf_counter()
-        for i, out in enumerate(pipeline.upscale_stream(model, decoded, args.scale, depth=args.depth, output_size=target)):
+        for i, out in enumerate(pipeline.upscale_stream(model, decoded, args.scale, depth=args.depth, output_size=target,
+                                                        keep_alpha=args.keep_alpha)):
             now = time.perf_counter()
             durations[mine[i]] = now - last   # (time between results: the stream's rate, not one image's latency)
             writes.append(pool.submit(write_rgb, out, os.path.join(args.output_path, output_name(mine[i]))))
