@@ -63,7 +63,13 @@ int larva_step_prologue(const float* const* w, float* const* wpk_fwd, float* con
  * mask (mask) and the skip-connection gradient adds (res0/res1) fused.
  * src: n_src (<= 8) tensors [N][cin_per_src][H][W] (cin_per_src % 8 == 0) read as one
  * channel-concatenated input.  cout in {32, 48, 64}.
- * Epilogue order: +bias -> relu -> (mask > 0 ? v : 0) -> +res0 -> +res1.
+ * Epilogue order: +bias -> relu -> (mask <= 0 ? 0 : v) -> +res0 -> +res1.
+ * Non-finite values follow torch: relu is `v < 0 ? 0 : v` (torch.relu: a NaN stays NaN, +Inf stays, -Inf and -0.0 give
+ * what torch gives), and the mask passes v wherever !(mask <= 0) (ATen's threshold_backward: a NaN mask element passes
+ * the gradient, as do +Inf and every positive value; -Inf, -0.0, +0.0 and negatives give +0.0).  bias, res0, res1 and base
+ * are plain fp32 additions: a NaN or Inf in one of their elements reaches exactly that output element (that output
+ * channel for bias).  A NaN or Inf activation reaches the 3 x 3 neighbourhood of its pixel in every output channel of its
+ * own image and nothing else.  Every store path and tiling behaves the same.
  * mode 0: out [N][cout][H][W]; supported fusions: none | relu | mask | res0 | res0+res1.
  * mode 1: out [N][cout/16][4H][4W] = PixelShuffle(4)(conv) (+ base, same shape, may be NULL).
  * Alignment.  pitch % 4 == 0 with wpk, every src, the mode-0 out, res0, res1 and mask 16-byte aligned takes the 16-byte

@@ -917,8 +917,8 @@ __device__ __forceinline__ void run_role(const ConvArgs& a, float* smem, int ct0
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               float o = v[r];
-              if constexpr (EPI == kEpiRelu) o = fmaxf(o, 0.f);
-              if constexpr (EPI == kEpiMask) o = (aux[0][c][p][r] > 0.f) ? o : 0.f;
+              if constexpr (EPI == kEpiRelu) o = o < 0.f ? 0.f : o;   // torch.relu: NaN stays NaN (fmaxf would return 0)
+              if constexpr (EPI == kEpiMask) o = (aux[0][c][p][r] <= 0.f) ? 0.f : o;   // threshold_backward: a NaN mask passes
               if constexpr (EPI == kEpiRes1 || EPI == kEpiRes2) o += aux[0][c][p][r];
               if constexpr (EPI == kEpiRes2) o += aux[1][c][p][r];
               v[r] = (kInterior || xb + r < k.W) ? o : 0.f;   // columns [W, pitch) are kept at zero for the next layer
@@ -965,8 +965,8 @@ __device__ __forceinline__ void run_role(const ConvArgs& a, float* smem, int ct0
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             float o = v[r];
-            if constexpr (EPI == kEpiRelu) o = fmaxf(o, 0.f);
-            if constexpr (EPI == kEpiMask) o = (aux[0][c][p][r] > 0.f) ? o : 0.f;
+            if constexpr (EPI == kEpiRelu) o = o < 0.f ? 0.f : o;   // torch.relu: NaN stays NaN (fmaxf would return 0)
+            if constexpr (EPI == kEpiMask) o = (aux[0][c][p][r] <= 0.f) ? 0.f : o;   // threshold_backward: a NaN mask passes
             if constexpr (EPI == kEpiRes1 || EPI == kEpiRes2) o += aux[0][c][p][r];
             if constexpr (EPI == kEpiRes2) o += aux[1][c][p][r];
             o = real ? o : 0.f;

@@ -100,6 +100,82 @@ def assert_bits_equal(got, ref, what):
     raise AssertionError("\n".join(lines))
 
 
+# ---------------------------------------------------------------- NaN / Inf (tests/test_nonfinite.py)
+CLASS_NAMES = ("finite", "+Inf", "-Inf", "NaN")
+
+
+def poison(a, positions, value):
+    """A copy of `a` with `value` (NaN, +Inf or -Inf) at the listed index tuples."""
+    v = float(value)
+    if np.isfinite(v):
+        raise AssertionError("test set-up: a poison is NaN, +Inf or -Inf, not %r" % (value,))
+    out = np.array(a, copy=True)
+    for pos in positions:
+        out[tuple(int(i) for i in pos)] = v
+    return out
+
+
+def unpoisoned(a, positions):
+    """The clean stand-in the exactness precondition is asserted on: `a` with its largest magnitude at `positions` (the
+    finite outputs of the poisoned run are sums of a subset of the terms of this one, so its bound covers them)."""
+    out = np.array(a, copy=True)
+    big = np.abs(out[np.isfinite(out)]).max() if np.isfinite(out).any() else 0
+    for pos in positions:
+        out[tuple(int(i) for i in pos)] = big
+    return out
+
+
+def class_map(a):
+    """uint8 per element: 0 finite, 1 +Inf, 2 -Inf, 3 NaN."""
+    a = _np(a)
+    with np.errstate(invalid="ignore"):
+        return (np.isposinf(a) * 1 + np.isneginf(a) * 2 + np.isnan(a) * 3).astype(np.uint8)
+
+
+def assert_equal_with_nonfinite(got, ref, what):
+    """assert_bits_equal, except that where `ref` is NaN `got` must be a NaN of any payload and sign.  Everywhere else,
+    +-Inf included, the bits must match.  On a mismatch: the count, got's and ref's elements per class (finite, +Inf,
+    -Inf, NaN), the first four indices and got / expected at each of them."""
+    g = _np(got)
+    r = _np(ref)
+    assert g.shape == r.shape, "%s: shape %s, expected %s" % (what, g.shape, r.shape)
+    assert g.dtype.kind == "f", "%s: %s is not a float type" % (what, g.dtype)
+    if r.dtype != g.dtype:
+        with np.errstate(over="ignore", invalid="ignore"):
+            r = r.astype(g.dtype)
+    view = {4: np.uint32, 2: np.uint16, 8: np.uint64}[g.dtype.itemsize]
+    gb, rb = g.view(view), r.view(view)
+    rnan = np.isnan(r)
+    wrong = np.where(rnan, ~np.isnan(g), gb != rb)
+    if not wrong.any():
+        return
+    bad = np.argwhere(wrong)
+    cg, cr = class_map(g), class_map(r)
+    lines = ["%s: %d of %d elements differ" % (what, len(bad), g.size),
+             "  got      " + ", ".join("%s %d" % (nm, int((cg == k).sum())) for k, nm in enumerate(CLASS_NAMES)),
+             "  expected " + ", ".join("%s %d" % (nm, int((cr == k).sum())) for k, nm in enumerate(CLASS_NAMES))]
+    for idx in bad[:4]:
+        t = tuple(int(i) for i in idx)
+        lines.append("  at %s got %r (0x%x) expected %r (0x%x)" % (list(t), g[t].item(), int(gb[t]), r[t].item(), int(rb[t])))
+    raise AssertionError("\n".join(lines))
+
+
+def mask_passes(mask):
+    """ATen's threshold_backward predicate: the gradient passes wherever !(mask <= 0) -- NaN and +Inf pass."""
+    with np.errstate(invalid="ignore"):
+        return ~(np.asarray(mask) <= 0)
+
+
+def conv_footprint(shape, positions, radius=1):
+    """Boolean [N][H][W]: the pixels whose 3 x 3 neighbourhood holds one of `positions` ((n, c, y, x) tuples) -- the
+    outputs of a 3 x 3 conv (any output channel) that depend on those elements."""
+    n, h, w = shape
+    fp = np.zeros((n, h, w), bool)
+    for (i, _, y, x) in positions:
+        fp[i, max(0, y - radius):y + radius + 1, max(0, x - radius):x + radius + 1] = True
+    return fp
+
+
 # ---------------------------------------------------------------- single operations (float64)
 def _t(a):
     return torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64)))
@@ -113,39 +189,47 @@ def conv_sum_bound(xs, w, bias=None, res0=None, res1=None):
     return amax * wsum + extra
 
 
-def conv(xs, w, bias=None, relu=False, mask=None, res0=None, res1=None):
+def conv(xs, w, bias=None, relu=False, mask=None, res0=None, res1=None, nonfinite=False):
     """3x3 conv (stride 1, zero padding 1) over the channel concatenation of `xs` with the library's epilogue order
-    + bias -> relu -> (mask > 0 ? v : 0) -> + res0 -> + res1 -> (float64 [N][cout][H][W], inter)."""
+    + bias -> relu -> (mask > 0 ? v : 0) -> + res0 -> + res1 -> (float64 [N][cout][H][W], inter).
+    nonfinite=True: operands may hold NaN / Inf, the rules are torch's (relu keeps NaN -- np.maximum does --, the mask
+    passes where !(mask <= 0)) and `inter` is None: the precondition belongs to the clean operands (`unpoisoned`)."""
     if isinstance(xs, np.ndarray):
         xs = [xs]
     x = _t(np.concatenate(xs, axis=1))
     y = F.conv2d(x, _t(w), None if bias is None else _t(bias), padding=1).numpy()
-    inter = [y.copy(), conv_sum_bound(xs, w, bias, res0, res1)]
+    inter = None if nonfinite else [y.copy(), conv_sum_bound(xs, w, bias, res0, res1)]
     if relu:
         y = np.maximum(y, 0.0)
-    if mask is not None:
+    if mask is not None and nonfinite:
+        y = np.where(mask_passes(mask), y, 0.0)
+    elif mask is not None:
         y = np.where(np.asarray(mask) > 0, y, 0.0)    # (a masked -x stays +0.0, as the kernel's select does)
     if res0 is not None:
         y = y + np.asarray(res0, np.float64)
     if res1 is not None:
         y = y + np.asarray(res1, np.float64)
-    inter.append(y)
+    if inter is not None:
+        inter.append(y)
     return y, inter
 
 
-def dgrad(dy, w, mask=None, res0=None, res1=None):
+def dgrad(dy, w, mask=None, res0=None, res1=None, nonfinite=False):
     """Input gradient of the 3x3 conv: dx[n, ci] = sum_co corr(dy[n, co], w[co, ci] mirrored) -> (float64, inter); with
-    the ReLU-backward mask and the skip gradients the library fuses into it."""
+    the ReLU-backward mask and the skip gradients the library fuses into it.  nonfinite: as for conv()."""
     dx = F.conv_transpose2d(_t(dy), _t(w), padding=1).numpy()
     wt = np.asarray(w, np.float64).transpose(1, 0, 2, 3)
-    inter = [dx.copy(), conv_sum_bound([dy], wt, None, res0, res1)]
-    if mask is not None:
+    inter = None if nonfinite else [dx.copy(), conv_sum_bound([dy], wt, None, res0, res1)]
+    if mask is not None and nonfinite:
+        dx = np.where(mask_passes(mask), dx, 0.0)
+    elif mask is not None:
         dx = np.where(np.asarray(mask) > 0, dx, 0.0)
     if res0 is not None:
         dx = dx + np.asarray(res0, np.float64)
     if res1 is not None:
         dx = dx + np.asarray(res1, np.float64)
-    inter.append(dx)
+    if inter is not None:
+        inter.append(dx)
     return dx, inter
 
 
@@ -182,9 +266,11 @@ def pad_channels(a, cpad):
 
 
 def l1_sign_grad(out, truth, g):
-    """sign(out - truth) * g with sign(0) = +0.0, float32."""
-    d = np.asarray(out, np.float64) - np.asarray(truth, np.float64)
-    return np.where(d > 0, np.float32(g), np.where(d < 0, np.float32(-g), np.float32(0.0))).astype(np.float32)
+    """sign(out - truth) * g with sign(0) = +0.0, float32; torch's sign on non-finite data: a NaN difference (NaN
+    operand, Inf - Inf) gives +0.0, +-Inf differences give +-g."""
+    with np.errstate(invalid="ignore"):
+        d = np.asarray(out, np.float64) - np.asarray(truth, np.float64)
+        return np.where(d > 0, np.float32(g), np.where(d < 0, np.float32(-g), np.float32(0.0))).astype(np.float32)
 
 
 def f16_round(v):
