@@ -29,12 +29,12 @@ world and the sums are all-reduced, as validate.py does."""
 import argparse
 import collections
 import concurrent.futures
-import importlib
 import os
 import time
 
 from . import dist as ldist
-from .upscale_images import _prefetched, exit_output_name, io_threads, list_pngs, output_name, read_rgb, shard, write_rgb
+from .upscale_images import (_prefetched, exit_output_name, io_threads, list_pngs, output_name, prepare_model, read_rgb, shard,
+                             write_rgb)
 
 
 def build_parser():
@@ -166,15 +166,7 @@ def main(argv=None):
     begin = time.perf_counter()
     if mine:   # (an empty shard launches nothing and prepares no model)
         from . import pipeline
-        print("prepare model - %s" % args.model)
-        model = importlib.import_module("larvanet_amd.models." + args.model).create_model()
-        _, remaining = model.parse_args(remaining)
-        model.prepare(is_training=False, scales=[args.scale], global_step=args.restore_global_step)
-        if remaining:
-            print("WARNING: found unhandled arguments: %s" % remaining)
-        if args.restore_path is not None:
-            model.restore(ckpt_path=args.restore_path, target=args.restore_target)
-            print("restored the model")
+        model = prepare_model(args, remaining)
         device = model.device
         if args.all_exits:
             model._check_exits()   # (a model without per-body exits or --self_ensemble: refused before any image is read)

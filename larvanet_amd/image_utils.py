@@ -110,6 +110,28 @@ def check_output_size(output_size, in_h, in_w):
     return check_resize(in_h, in_w, h, w)
 
 
+# ------------------------------------------------------------------ one image / one frame of an entry point's or a stream's input
+def check_u8_image(a, who, channels, also_rgba=False):
+    """A decoded image handed to `who`: a uint8 (H, W, channels) numpy array of at least one pixel, else TypeError /
+    ValueError.  also_rgba: (H, W, 4) passes too (upscale_stream with keep_alpha), and the refusal says so."""
+    if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
+        raise TypeError("larvanet_amd: %s takes uint8 numpy arrays (decoded images), got %s"
+                        % (who, getattr(a, "dtype", type(a).__name__),))
+    if a.ndim != 3 or a.shape[2] not in ((channels, 4) if also_rgba else (channels,)) or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("larvanet_amd: %s takes (H, W, %d) images%s, got shape %s"
+                         % (who, channels, " and, with keep_alpha, (H, W, 4) ones" if also_rgba else "", a.shape,))
+
+
+def check_i420_frame(f, who, nbytes, width, height, one_size=False):
+    """An I420 frame of width x height handed to `who`: a flat uint8 numpy buffer of nbytes (i420_frame_bytes), else
+    TypeError / ValueError.  one_size: the caller takes frames of one size per call and says so."""
+    if not isinstance(f, np.ndarray) or f.dtype != np.uint8:
+        raise TypeError("larvanet_amd: %s takes uint8 numpy frames, got %s" % (who, getattr(f, "dtype", type(f).__name__),))
+    if f.ndim != 1 or f.size != nbytes:
+        raise ValueError("larvanet_amd: an I420 frame of %d x %d is a flat buffer of %d bytes%s, got shape %s"
+                         % (width, height, nbytes, " (one size per call)" if one_size else "", f.shape,))
+
+
 def _keys_cubic(x):
     a = -0.5
     x = np.abs(x)

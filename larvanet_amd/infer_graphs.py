@@ -1,5 +1,5 @@
 """Which grad-free forward a call runs (Form) and the rule that decides when its shape is worth a hipGraph (GraphTable).
-Neither touches the GPU: the plugin (models/LarvaNet.py) hands the table the callables that do."""
+Neither touches the GPU: the plugin (inference.InferenceMixin._eager_or_graph) hands the table the callables that do."""
 from typing import NamedTuple
 
 

@@ -38,6 +38,9 @@ import collections
 import numpy as np
 import torch
 
+from . import kernels as K
+from .image_utils import check_i420_frame, check_output_size, check_u8_image, i420_frame_bytes
+
 
 class _Slot:
     """The staging buffers of one image in flight."""
@@ -45,8 +48,8 @@ class _Slot:
     def __init__(self, device, copy_stream):
         self.device = device
         self.copy_stream = copy_stream
-        self.pin_in = self.pin_out = self.dev_in = self.dev_out = None
-        self.pin_truth = self.dev_truth = self.pin_record = self.dev_record = None   # evaluate_stream only
+        self.pin, self.dev = {}, {}   # "in", "out" and (evaluate_stream only) "truth": the flat pinned / device buffers
+        self.pin_record = self.dev_record = None   # evaluate_stream only
         self.pin_flag = torch.zeros(1, dtype=torch.int32, pin_memory=True)
         self.dev_flag = torch.zeros(1, dtype=torch.int32, device=device)
         self.dev_flag.record_stream(copy_stream)
@@ -66,23 +69,15 @@ class _Slot:
         buf.record_stream(self.copy_stream)
         return buf
 
-    def views_in(self, shape):
+    def views(self, which, shape, host=True):
+        """(pinned view, device view) at `shape` of the slot's `which` buffers, grown as needed; host=False: the device
+        view alone (an input made on the device has no host side)."""
         n = int(np.prod(shape))
-        self.pin_in = self._grown(self.pin_in, n, True)
-        self.dev_in = self._grown(self.dev_in, n, False)
-        return self.pin_in[:n].view(shape), self.dev_in[:n].view(shape)
-
-    def view_made_in(self, shape):
-        """The device input buffer alone: an input made on the device has no host side."""
-        n = int(np.prod(shape))
-        self.dev_in = self._grown(self.dev_in, n, False)
-        return self.dev_in[:n].view(shape)
-
-    def views_truth(self, shape):
-        n = int(np.prod(shape))
-        self.pin_truth = self._grown(self.pin_truth, n, True)
-        self.dev_truth = self._grown(self.dev_truth, n, False)
-        return self.pin_truth[:n].view(shape), self.dev_truth[:n].view(shape)
+        if host:
+            self.pin[which] = self._grown(self.pin.get(which), n, True)
+        self.dev[which] = self._grown(self.dev.get(which), n, False)
+        dev = self.dev[which][:n].view(shape)
+        return (self.pin[which][:n].view(shape), dev) if host else dev
 
     def records(self, words):
         if self.dev_record is None:
@@ -91,28 +86,148 @@ class _Slot:
             self.dev_record.record_stream(self.copy_stream)
         return self.pin_record, self.dev_record
 
-    def views_out(self, shape):
-        n = int(np.prod(shape))
-        self.pin_out = self._grown(self.pin_out, n, True)
-        self.dev_out = self._grown(self.dev_out, n, False)
-        return self.pin_out[:n].view(shape), self.dev_out[:n].view(shape)
-
 
 def _check_image(a, who="upscale_stream", keep_alpha=False):
-    if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
-        raise TypeError("larvanet_amd: %s takes uint8 numpy arrays (decoded images), got %s"
-                        % (who, getattr(a, "dtype", type(a).__name__),))
-    if keep_alpha and a.ndim == 3 and a.shape[2] == 4 and a.shape[0] >= 1 and a.shape[1] >= 1:
-        return
-    if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
-        raise ValueError("larvanet_amd: %s takes (H, W, 3) images%s, got shape %s"
-                         % (who, " and, with keep_alpha, (H, W, 4) ones" if keep_alpha else "", a.shape,))
+    check_u8_image(a, who, 3, also_rgba=keep_alpha)
+
+
+def _check_frame(f, nbytes, width, height):
+    check_i420_frame(f, "upscale_yuv_stream", nbytes, width, height)
 
 
 def _check_target(output_size):
     """output_size as given -> None or (height, width); the ratio is checked per image, its size being known only then."""
-    from .image_utils import check_output_size
     return None if output_size is None else check_output_size(output_size, 1, 1)
+
+
+def _check_depth(depth, who):
+    depth = int(depth)
+    if depth < 1:
+        raise ValueError("larvanet_amd: %s needs depth >= 1" % who)
+    return depth
+
+
+def _require_hip_model(model, who):
+    if model.device.type != "cuda":
+        raise RuntimeError("larvanet_amd: %s only runs on a HIP device (MI355X); there is no CPU fallback" % who)
+
+
+class _Stage:
+    """What _stream (the pipeline itself, below) asks about one kind of item, one subclass per public stream:
+      admit(item) -> job            the item checked and sized, before anything of it is launched; job[0] is the array
+      fill(slot, job) -> (copies, buffers)    the item written into the slot's pinned buffers: [(device view, pinned view)]
+                                    to copy in on the copy stream, and the device views launch() works on
+      launch(slot, job, *buffers)   the launches on the compute stream, through the plugin's composers (_infer_rgb,
+                                    _infer_rgba, _infer_i420) with model._infer_u8_images as the forward; sets slot.out_shape
+      outputs(slot) -> [(pinned view, device view)]    what the copy stream brings back
+      result(slot)                  what the stream yields for the item, from the pinned buffers
+    Written out here: one array in as a batch of one, and the slot's output buffer back (both upscaling streams)."""
+
+    def fill(self, slot, job):
+        pin_in, dev_in = slot.views("in", (1,) + tuple(job[0].shape))
+        np.copyto(pin_in.numpy()[0], job[0])
+        return [(dev_in, pin_in)], (dev_in,)
+
+    def outputs(self, slot):
+        return [slot.views("out", slot.out_shape)]
+
+    def result(self, slot):
+        return np.array(slot.views("out", slot.out_shape)[0].numpy()[0])
+
+
+class _UpscaleStage(_Stage):
+    """upscale_stream: uint8 (H, W, 3) images and, with keep_alpha, (H, W, 4) ones; with target every result has that size."""
+
+    def __init__(self, model, target, keep_alpha):
+        self.model, self.target, self.keep_alpha = model, target, keep_alpha
+
+    def admit(self, image):
+        _check_image(image, keep_alpha=self.keep_alpha)
+        self.model._output_size(self.target, image.shape[0], image.shape[1])
+        return (image,)
+
+    def launch(self, slot, job, dev_in):
+        m, target, image = self.model, self.target, job[0]
+        slot.out_shape = (1,) + (target or tuple(m.scale * v for v in image.shape[:2])) + (image.shape[2],)
+        dev_out = slot.views("out", slot.out_shape)[1]
+        if image.shape[2] == 4:   # RGBA: split -> forward over colour (and alpha) -> merged into the slot's buffer
+            m._infer_rgba(dev_in, [bool(image[..., 3].min() == 255)],
+                          lambda planes: m._infer_rgb(planes, target, m._infer_u8_images), out=dev_out)
+        else:   # (the x8 self-ensemble under --self_ensemble; resized, or else copied, straight into the slot's own buffer)
+            m._infer_rgb(dev_in, target, m._infer_u8_images, out=dev_out)
+
+
+class _VideoStage(_Stage):
+    """upscale_yuv_stream: flat I420 frames of `size` = (width, height), or (frame, width, height) triples; a frame is a
+    batch of one, [1][frame bytes], on the way in and on the way out."""
+
+    def __init__(self, model, target, size, matrix, full_range):
+        self.model, self.target, self.size, self.matrix, self.full_range = model, target, size, matrix, full_range
+
+    def admit(self, item):
+        frame, fw, fh = (item,) + self.size if self.size is not None else item
+        fw, fh = int(fw), int(fh)
+        _check_frame(frame, i420_frame_bytes(fw, fh), fw, fh)
+        self.model._output_size(self.target, fh, fw)
+        return frame, fw, fh
+
+    def launch(self, slot, job, dev_in):   # frame -> float planes -> forward -> HR frame, written into the slot's own buffer
+        m, (_, fw, fh) = self.model, job
+        hr_h, hr_w = self.target or (m.scale * fh, m.scale * fw)
+        slot.out_shape = (1, i420_frame_bytes(hr_w, hr_h))
+        m._infer_i420(dev_in, fw, fh, self.matrix, self.full_range, self.target, m._infer_u8_images,
+                      out=slot.views("out", slot.out_shape)[1])
+
+
+class _EvaluateStage(_Stage):
+    """evaluate_stream: (input, truth) pairs of uint8 (H, W, 3) images, the input None where it is made from the truth on
+    the device; the 64-byte record comes back, and the image when `keep`."""
+
+    def __init__(self, model, shave, channel, ssim, keep):
+        self.model, self.shave, self.channel, self.ssim, self.keep = model, shave, channel, ssim, keep
+
+    def admit(self, pair):
+        image, truth = pair
+        _check_image(truth, "evaluate_stream")
+        if image is None:   # the input is made from the truth on the device
+            in_shape = K.bicubic_down_size(truth.shape[0], truth.shape[1], self.model.scale) + (3,)
+        else:
+            _check_image(image, "evaluate_stream")
+            in_shape = tuple(image.shape)
+        K.metric_window((self.model.scale * in_shape[0], self.model.scale * in_shape[1]), truth.shape, self.shave, self.ssim)
+        return image, truth, in_shape
+
+    def fill(self, slot, job):
+        image, truth, in_shape = job
+        copies = []
+        if image is None:
+            dev_in = slot.views("in", (1,) + in_shape, host=False)
+        else:
+            pin_in, dev_in = slot.views("in", (1,) + in_shape)
+            np.copyto(pin_in.numpy()[0], image)
+            copies.append((dev_in, pin_in))
+        pin_truth, dev_truth = slot.views("truth", tuple(truth.shape))
+        np.copyto(pin_truth.numpy(), truth)
+        copies.append((dev_truth, pin_truth))
+        return copies, (dev_in, dev_truth)
+
+    def launch(self, slot, job, dev_in, dev_truth):
+        m = self.model
+        if job[0] is None:
+            K.bicubic_down_u8(dev_truth, m.scale, out=dev_in[0])
+        out = m._infer_rgb(dev_in, None, m._infer_u8_images)
+        slot.out_shape = tuple(out.shape)
+        if self.keep:
+            slot.views("out", slot.out_shape)[1].copy_(out)
+        # (scored where the forward left it: nothing else runs on this stream in between)
+        K.u8_metrics(out[0], dev_truth, self.shave, self.channel, self.ssim, result=slot.records(K.METRIC_RESULT_WORDS)[1])
+
+    def outputs(self, slot):
+        return (super().outputs(slot) if self.keep else []) + [(slot.pin_record, slot.dev_record)]
+
+    def result(self, slot):
+        result = K.metrics_from_record(slot.pin_record.numpy().copy())
+        return (result, super().result(slot)) if self.keep else result
 
 
 def upscale_stream(model, images, scale, depth=2, output_size=None, keep_alpha=False):
@@ -125,15 +240,11 @@ def upscale_stream(model, images, scale, depth=2, output_size=None, keep_alpha=F
     Under --precision fp16 an image whose activations overflow raises FloatingPointError when its turn to be yielded
     comes; the images before it have been yielded.  The yielded arrays are the caller's (copies of the pinned staging
     buffers)."""
-    depth = int(depth)
-    if depth < 1:
-        raise ValueError("larvanet_amd: upscale_stream needs depth >= 1")
+    depth = _check_depth(depth, "upscale_stream")
     target = _check_target(output_size)
-    if int(scale) != model.scale:
-        raise ValueError("larvanet_amd: this model upscales by %d, not by %r" % (model.scale, scale))
-    if model.device.type != "cuda":
-        raise RuntimeError("larvanet_amd: upscale_stream only runs on a HIP device (MI355X); there is no CPU fallback")
-    return _stream(model, images, depth, target=target, keep_alpha=bool(keep_alpha))
+    model._check_scale(scale)
+    _require_hip_model(model, "upscale_stream")
+    return _stream(model, images, depth, _UpscaleStage(model, target, bool(keep_alpha)))
 
 
 def evaluate_stream(model, pairs, scale, shave=None, channel="y", ssim=True, depth=2, keep_images=False):
@@ -147,29 +258,15 @@ def evaluate_stream(model, pairs, scale, shave=None, channel="y", ssim=True, dep
     `scale`, made on the device (kernels.bicubic_down_u8: the truth's top-left (H // scale) scale x (W // scale) scale
     pixels, the window the metrics crop to anyway); its result equals the pair (image_utils.bicubic_downscale_u8(truth,
     scale), truth)'s."""
-    from . import kernels as K
-    depth = int(depth)
-    if depth < 1:
-        raise ValueError("larvanet_amd: evaluate_stream needs depth >= 1")
-    if int(scale) != model.scale:
-        raise ValueError("larvanet_amd: this model upscales by %d, not by %r" % (model.scale, scale))
+    depth = _check_depth(depth, "evaluate_stream")
+    model._check_scale(scale)
     if channel not in K.METRIC_CHANNELS:
         raise ValueError("larvanet_amd: channel must be 'y' or 'rgb', got %r" % (channel,))
     shave = model.scale if shave is None else int(shave)
     if shave < 0:
         raise ValueError("larvanet_amd: metrics need shave >= 0, got %d" % shave)
-    if model.device.type != "cuda":
-        raise RuntimeError("larvanet_amd: evaluate_stream only runs on a HIP device (MI355X); there is no CPU fallback")
-    return _stream(model, pairs, depth, {"shave": shave, "channel": channel, "ssim": bool(ssim), "keep": bool(keep_images)})
-
-
-def _check_frame(f, nbytes, width, height):
-    if not isinstance(f, np.ndarray) or f.dtype != np.uint8:
-        raise TypeError("larvanet_amd: upscale_yuv_stream takes uint8 numpy frames, got %s"
-                        % (getattr(f, "dtype", type(f).__name__),))
-    if f.ndim != 1 or f.size != nbytes:
-        raise ValueError("larvanet_amd: an I420 frame of %d x %d is a flat buffer of %d bytes, got shape %s"
-                         % (width, height, nbytes, f.shape,))
+    _require_hip_model(model, "evaluate_stream")
+    return _stream(model, pairs, depth, _EvaluateStage(model, shave, channel, bool(ssim), bool(keep_images)))
 
 
 def upscale_yuv_stream(model, frames, scale, width=None, height=None, matrix="bt601", full_range=False, depth=2,
@@ -180,9 +277,7 @@ def upscale_yuv_stream(model, frames, scale, width=None, height=None, matrix="bt
     staging slots, one copy stream, at most `depth` frames in flight; under --precision fp16 a frame whose activations
     overflow raises FloatingPointError when its turn to be yielded comes, the frames before it have been yielded.
     output_size = (height, width): the HR frames are of that size, as upscale_yuv420's with the same argument."""
-    depth = int(depth)
-    if depth < 1:
-        raise ValueError("larvanet_amd: upscale_yuv_stream needs depth >= 1")
+    depth = _check_depth(depth, "upscale_yuv_stream")
     target = _check_target(output_size)
     if width is not None and height is not None:
         model._output_size(target, height, width)   # (one input size: the ratio is refused here, before any frame)
@@ -190,21 +285,14 @@ def upscale_yuv_stream(model, frames, scale, width=None, height=None, matrix="bt
         raise ValueError("larvanet_amd: upscale_yuv_stream takes width and height, or neither (items are then "
                          "(frame, width, height) triples)")
     model._check_yuv_args(1 if width is None else width, 1 if height is None else height, matrix, full_range, scale)
-    if model.device.type != "cuda":
-        raise RuntimeError("larvanet_amd: upscale_yuv_stream only runs on a HIP device (MI355X); there is no CPU fallback")
+    _require_hip_model(model, "upscale_yuv_stream")
     size = None if width is None else (int(width), int(height))
-    return _stream(model, frames, depth, yuv={"size": size, "matrix": matrix, "full_range": bool(full_range)}, target=target)
+    return _stream(model, frames, depth, _VideoStage(model, target, size, matrix, bool(full_range)))
 
 
-def _stream(model, images, depth, score=None, yuv=None, target=None, keep_alpha=False):
-    """The pipeline of upscale_stream; with `score` (evaluate_stream's settings) the items are (input, truth) pairs; with
-    `yuv` (upscale_yuv_stream's settings) they are I420 frames, or (frame, width, height) triples; with `target` = (height,
-    width) the two upscaling streams resize every result to it; with keep_alpha upscale_stream takes RGBA images too."""
-    if score is not None or yuv is not None or target is not None or keep_alpha:
-        from . import kernels as K
-    if yuv is not None:
-        from .image_utils import i420_frame_bytes
-    keep = score is None or score["keep"]
+def _stream(model, items, depth, stage):
+    """The pipeline itself, for the items and the work `stage` describes: the slots, the copy stream, the three events of
+    a slot, and the order in which both streams are fed."""
     compute = torch.cuda.current_stream()
     copy = torch.cuda.Stream()
     free = [_Slot(model.device, copy) for _ in range(depth)]
@@ -217,11 +305,8 @@ def _stream(model, images, depth, score=None, yuv=None, target=None, keep_alpha=
             return
         with torch.cuda.stream(copy):
             copy.wait_event(slot.fwd)
-            if keep:
-                pin_out, dev_out = slot.views_out(slot.out_shape)
-                pin_out.copy_(dev_out, non_blocking=True)
-            if score is not None:
-                slot.pin_record.copy_(slot.dev_record, non_blocking=True)
+            for pinned, dev in stage.outputs(slot):
+                pinned.copy_(dev, non_blocking=True)
             if fp16:
                 slot.pin_flag.copy_(slot.dev_flag, non_blocking=True)
             slot.done.record(copy)
@@ -232,88 +317,28 @@ def _stream(model, images, depth, score=None, yuv=None, target=None, keep_alpha=
         slot.done.synchronize()
         if fp16 and int(slot.pin_flag[0]):
             raise model.overflow_error()
-        out = np.array(slot.views_out(slot.out_shape)[0].numpy()[0]) if keep else None
-        if yuv is not None:
-            out = out[0]   # (the frame itself, 1-D)
-        result = None if score is None else K.metrics_from_record(slot.pin_record.numpy().copy())
+        result = stage.result(slot)
         free.append(slot)
-        if score is None:
-            return out
-        return (result, out) if keep else result
+        return result
 
     try:
         with torch.no_grad():
             if fp16:
                 model_flag.zero_()
-            for image in images:
-                if yuv is not None:
-                    image, fw, fh = (image,) + yuv["size"] if yuv["size"] is not None else image
-                    fw, fh = int(fw), int(fh)
-                    _check_frame(image, i420_frame_bytes(fw, fh), fw, fh)
-                    model._output_size(target, fh, fw)
-                    image = image[None]   # (a batch of one frame: [1][frame bytes])
-                elif score is None:
-                    _check_image(image, keep_alpha=keep_alpha)
-                    model._output_size(target, image.shape[0], image.shape[1])
-                else:
-                    image, truth = image
-                    _check_image(truth, "evaluate_stream")
-                    if image is None:   # the input is made from the truth on the device
-                        in_shape = K.bicubic_down_size(truth.shape[0], truth.shape[1], model.scale) + (3,)
-                    else:
-                        _check_image(image, "evaluate_stream")
-                        in_shape = tuple(image.shape)
-                    K.metric_window((model.scale * in_shape[0], model.scale * in_shape[1]), truth.shape,
-                                    score["shave"], score["ssim"])
+            for item in items:
+                job = stage.admit(item)
                 if len(inflight) == depth:
                     yield retire(inflight.popleft())
                 slot = free.pop()
-                made = score is not None and image is None
-                shape = (1,) + (in_shape if made else tuple(image.shape))
-                if made:
-                    dev_in = slot.view_made_in(shape)
-                else:
-                    pin_in, dev_in = slot.views_in(shape)
-                    np.copyto(pin_in.numpy()[0], image)
-                if score is not None:
-                    pin_truth, dev_truth = slot.views_truth(tuple(truth.shape))
-                    np.copyto(pin_truth.numpy(), truth)
+                copies, buffers = stage.fill(slot, job)
                 with torch.cuda.stream(copy):
-                    if not made:
-                        dev_in.copy_(pin_in, non_blocking=True)
-                    if score is not None:
-                        dev_truth.copy_(pin_truth, non_blocking=True)
+                    for dev, pinned in copies:
+                        dev.copy_(pinned, non_blocking=True)
                     slot.h2d.record(copy)
                 if inflight:   # the previous image's way back, queued behind this image's way in
                     issue_d2h(inflight[-1])
                 compute.wait_event(slot.h2d)
-                if made:
-                    K.bicubic_down_u8(dev_truth, model.scale, out=dev_in[0])
-                if yuv is not None:   # frame -> float planes -> forward -> HR frame, written into the slot's own buffer
-                    x = K.i420_to_rgb_f32(dev_in[0], fw, fh, yuv["matrix"], yuv["full_range"])
-                    out = model._infer_u8_images(x)
-                    if target is not None:
-                        out = K.resize_u8(out, target[0], target[1])
-                    slot.out_shape = (1, 1, i420_frame_bytes(out.shape[2], out.shape[1]))
-                    K.rgb_u8_to_i420(out, yuv["matrix"], yuv["full_range"], out=slot.views_out(slot.out_shape)[1][0])
-                elif dev_in.shape[3] == 4:   # RGBA: split -> forward over colour (and alpha) -> merged into the slot's buffer
-                    def infer(planes):
-                        out = model._infer_u8_images(planes)
-                        return out if target is None else K.resize_u8(out, target[0], target[1])
-                    slot.out_shape = (1,) + (target or tuple(model.scale * v for v in image.shape[:2])) + (4,)
-                    model._infer_rgba(dev_in, [bool(image[..., 3].min() == 255)], infer, out=slot.views_out(slot.out_shape)[1])
-                else:
-                    out = model._infer_u8_images(dev_in)   # (the x8 self-ensemble under --self_ensemble)
-                    if target is not None:   # (upscale_stream only: resized straight into the slot's own buffer)
-                        slot.out_shape = (1,) + target + (3,)
-                        K.resize_u8(out, target[0], target[1], out=slot.views_out(slot.out_shape)[1])
-                    else:
-                        slot.out_shape = tuple(out.shape)
-                        if keep:
-                            slot.views_out(slot.out_shape)[1].copy_(out)
-                if score is not None:   # (scored where the forward left it: nothing else runs on this stream in between)
-                    K.u8_metrics(out[0], dev_truth, score["shave"], score["channel"], score["ssim"],
-                                 result=slot.records(K.METRIC_RESULT_WORDS)[1])
+                stage.launch(slot, job, *buffers)
                 if fp16:   # this image's overflow verdict; the model's flag starts the next image clean
                     slot.dev_flag.copy_(model_flag)
                     model_flag.zero_()

@@ -71,13 +71,34 @@ def check_keep_alpha(args):
         raise ValueError("larvanet_amd.upscale_images: --keep_alpha together with --all_exits is not supported")
 
 
+def parsed_output_size(args):
+    """--output_size as (height, width), or None where the flag was not given; ValueError for a malformed value."""
+    return None if args.output_size is None else parse_output_size(args.output_size)
+
+
 def output_size_of(args):
     """--output_size as (height, width), or None; ValueError for a malformed value or together with --all_exits."""
-    if args.output_size is None:
-        return None
-    if args.all_exits:
+    if args.output_size is not None and args.all_exits:
         raise ValueError("larvanet_amd.upscale_images: --output_size together with --all_exits is not supported")
-    return parse_output_size(args.output_size)
+    return parsed_output_size(args)
+
+
+def prepare_model(args, remaining, log=None, import_module=None):
+    """The plugin --model names, made from the arguments the driver's own parser left over (`remaining`), prepared for
+    inference at --scale and restored from --restore_path: what upscale_images, upscale_video and evaluate do alike.
+    log: the file the progress lines go to (None: stdout).  import_module: what loads the plugin's module, by default this
+    module's importlib.import_module as it is when called; upscale_video hands in its own, which its tests replace to show
+    that no model is loaded before the input has been checked."""
+    print("prepare model - %s" % args.model, file=log)
+    model = (import_module or importlib.import_module)("larvanet_amd.models." + args.model).create_model()
+    _, remaining = model.parse_args(remaining)
+    model.prepare(is_training=False, scales=[args.scale], global_step=args.restore_global_step)
+    if remaining:
+        print("WARNING: found unhandled arguments: %s" % remaining, file=log)
+    if args.restore_path is not None:
+        model.restore(ckpt_path=args.restore_path, target=args.restore_target)
+        print("restored the model", file=log)
+    return model
 
 
 def png_size(path):
@@ -172,16 +193,7 @@ def main(argv=None):
             check_resize(in_h * args.scale, in_w * args.scale, *target)
 
     from . import pipeline
-    print("prepare model - %s" % args.model)
-    model = importlib.import_module("larvanet_amd.models." + args.model).create_model()
-    _, remaining = model.parse_args(remaining)
-    model.prepare(is_training=False, scales=[args.scale], global_step=args.restore_global_step)
-    if remaining:
-        print("WARNING: found unhandled arguments: %s" % remaining)
-    if args.restore_path is not None:
-        model.restore(ckpt_path=args.restore_path, target=args.restore_target)
-        print("restored the model")
-
+    model = prepare_model(args, remaining)
     if args.all_exits:
         model._check_exits()   # (a model without per-body exits or --self_ensemble: refused before any image is read)
     print("begin super-resolution")

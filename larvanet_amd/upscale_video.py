@@ -29,7 +29,8 @@ import threading
 import time
 
 from . import y4m
-from .image_utils import YUV_MATRICES, check_resize, parse_output_size
+from .image_utils import YUV_MATRICES, check_resize
+from .upscale_images import parsed_output_size, prepare_model
 
 _END = object()
 
@@ -60,10 +61,8 @@ def build_parser():
 def output_size_of(args, size=None):
     """--output_size as (height, width), or None; ValueError for a malformed value and, with the input's `size` = (width,
     height) known, for a target an axis of the upscaled frame would shrink by more than 4 to reach."""
-    if args.output_size is None:
-        return None
-    target = parse_output_size(args.output_size)
-    if size is not None:
+    target = parsed_output_size(args)
+    if target is not None and size is not None:
         check_resize(size[1] * args.scale, size[0] * args.scale, *target)
     return target
 
@@ -209,15 +208,7 @@ def main(argv=None):
         out_w, out_h = (size[0] * args.scale, size[1] * args.scale) if target is None else (target[1], target[0])
         print("video: %d x %d -> %d x %d, %s, %s range" % (size[0], size[1], out_w, out_h,
                                                           args.matrix, "full" if full_range else "limited"), file=log)
-        print("prepare model - %s" % args.model, file=log)
-        model = importlib.import_module("larvanet_amd.models." + args.model).create_model()
-        _, remaining = model.parse_args(remaining)
-        model.prepare(is_training=False, scales=[args.scale], global_step=args.restore_global_step)
-        if remaining:
-            print("WARNING: found unhandled arguments: %s" % remaining, file=log)
-        if args.restore_path is not None:
-            model.restore(ckpt_path=args.restore_path, target=args.restore_target)
-            print("restored the model", file=log)
+        model = prepare_model(args, remaining, log, importlib.import_module)
         out_raw = sys.stdout.buffer if args.output == "-" else open(args.output, "wb")
         try:
             t0 = time.perf_counter()

@@ -229,12 +229,20 @@ def test_one_rule_decides_eager_inference_and_the_direct_head_kernel(monkeypatch
     assert A.is_large_inference(1, 339, 510) and not A.is_large_inference(16, 48, 48)
     assert not A.is_large_inference(1, 250, 400) and A.is_large_inference(1, 250, 401)
     assert "is_large_inference" in inspect.getsource(L.LarvaNet._eager_or_graph)
-    m, went = L.create_model(), []   # _infer, _infer_u8 and _infer_ensemble all go through that one function
+    m, went = L.create_model(), []   # _infer, the streams' _infer_u8_images and _infer_checked all go through that one function
     monkeypatch.setattr(m, "_eager_or_graph", lambda x, form: went.append((id(x), tuple(form))))
     xf, x8 = torch.zeros(1, 3, 4, 4), torch.zeros(1, 4, 4, 3, dtype=torch.uint8)
+    want = [(id(xf), (False, False)), (id(x8), (True, False)), (id(xf), (False, True)), (id(x8), (True, True))]
     with torch.no_grad():
-        m._infer(xf), m._infer_u8(x8), m._infer_ensemble(xf), m._infer_ensemble(x8, True)
-    assert went == [(id(xf), (False, False)), (id(x8), (True, False)), (id(xf), (False, True)), (id(x8), (True, True))]
+        m._infer(xf), m._infer_u8_images(x8), m._infer_checked(xf, False, True)
+        m.parse_args(["--self_ensemble"])
+        m._infer_u8_images(x8)
+    assert went == want
+    del went[:]
+    with torch.no_grad():
+        for x, (u8, ensemble) in ((xf, (False, False)), (x8, (True, False)), (xf, (False, True)), (x8, (True, True))):
+            m._infer_checked(x, u8, ensemble)
+    assert went == want
     assert "is_large_inference" in inspect.getsource(A.HeadFn.forward)
     for ok, want in (("auto", "auto"), ("0", False), ("1", True)):
         monkeypatch.setenv("LARVA_HEAD_DIRECT", ok)
