@@ -53,6 +53,16 @@ def _lw():
     return PaddedWidth.current
 
 
+def refuse_grad_of(t, what, who):
+    """An input whose gradient torch's own operators would return and these nodes do not compute (the image the head and
+    the base interpolation read, the base image of a leg, the truth of a loss): asked for, it is refused.  A Function that
+    returns None for such an input hands autograd a silent zero.  Called by the modules, where the grad mode is visible
+    (inside Function.forward it is always off); under torch.no_grad() such a tensor passes."""
+    if t.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("larvanet_amd: the gradient of %s is not computed by %s; detach() it, or call under "
+                           "torch.no_grad()" % (what, who))
+
+
 class DualChain:
     """The dependent layer chain of a step (head -> 32 body convs forward, 32 dgrads backward) as TWO
     independent chains, one per half of the batch, on two streams.
@@ -362,7 +372,11 @@ class GradBucket:
     (no flatten / unflatten copies), and the optimizer sees ordinary p.grad tensors.
     Gradients are OVERWRITTEN by every backward (the reference zeroes them before each backward,
     models/LarvaNet.py:112-113, so the result is the same); zero_grad(set_to_none=True) would
-    detach the views and must not be used while a bucket is attached."""
+    detach the views and must not be used while a bucket is attached.
+    A parameter frozen (requires_grad_(False)) after the bucket was made ends it: intact() turns false, the next eager
+    step drops the bucket and autograd and torch's per-tensor AdamW, which skip that parameter, take over.  A step
+    captured BEFORE the freeze keeps what it captured (its launches still write and step the frozen parameter):
+    nothing is checked per replay; freeze before the first step, or capture again (prepare())."""
 
     def __init__(self, module, pcs):
         params = [p for p in module.parameters() if p.requires_grad]
@@ -381,7 +395,12 @@ class GradBucket:
             pc.grad_inplace = id(pc.weight) in owned and id(pc.bias) in owned
 
     def intact(self, module=None):
-        """False if somebody replaced or dropped a .grad (then fall back to autograd's own)."""
+        """False if somebody replaced or dropped a .grad or froze a parameter (then fall back to autograd's own)."""
+        return self.views_attached() and all(p.requires_grad for p, _ in self._pairs)
+
+    def views_attached(self):
+        """Is every .grad still its view of the flat buffer?  (What the optimizer asks before every flat step: a frozen
+        parameter has made the plugin drop the bucket, and with it the views, before the step gets there.)"""
         return all(p.grad is view for p, view in self._pairs)
 
     def span(self, tensors):
@@ -892,6 +911,17 @@ class LegFn(torch.autograd.Function):
         return (dfea, None, None, None) + tuple(dparams)
 
 
+def _term_gradient(gterm, gscale, numel):
+    """What the L1 backward kernels are handed for an exit's term whose gradient arrives from autograd (no seed known in
+    the forward pass) -> (device scalar g0, host factor): they write sign(out - truth) * g0 * factor / numel.
+    A finished scalar (0-d) receives the gradient of the mean itself.  A partial-sum term receives the gradient of its
+    ELEMENTS, the same for every element (whoever finishes it sums them and multiplies by 1 / numel, MeanTermsFn or
+    torch's own operators): element 0, with the kernel's 1 / numel taken out of the factor again."""
+    if gterm.dim() == 0:
+        return gterm.contiguous(), gscale
+    return gterm.as_strided((), ()), gscale * float(numel)
+
+
 class ExitFn(torch.autograd.Function):
     """One whole exit of the training step: LarvaLeg.forward followed by nn.L1Loss against the
     truth (models/LarvaNet.py:107-108).  Same kernels as LegFn + L1LossFn, but the backward
@@ -899,9 +929,10 @@ class ExitFn(torch.autograd.Function):
     (one fused launch instead of l1_bwd + pixel_unshuffle, no HR-layout gradient tensor).
     Returns (exit image, loss term); the image output carries no gradient path of its own.  With a divisor the term
     is the block partial sums of |out - truth| as they enter the mean over `divisor` exits, finished by MeanTermsFn
-    together with the other exits (see LossTerm); its gradient arrives unscaled and the 1/divisor is applied inside the
-    L1 backward kernel.  When the seed of backward is known (the plugin's step) the gradient is written in the same
-    pass as the partial sums, already unshuffled."""
+    together with the other exits (see LossTerm) or by torch's own operators (term.sum() * (1 / numel)); the gradient
+    of its elements arrives without the 1/divisor, which is applied inside the L1 backward kernel (_term_gradient).
+    When the seed of backward is known (the plugin's step) the gradient is written in the same pass as the partial
+    sums, already unshuffled, and whatever arrives in backward is ignored."""
 
     @staticmethod
     def forward(ctx, fea, base, truth, pcs, scale, divisor, w1, b1, w2, b2):
@@ -936,11 +967,10 @@ class ExitFn(torch.autograd.Function):
         if ctx.have_dyl:
             dyl = saved[2]
         else:
-            # (a partial-sum term receives its scalar gradient broadcast to its shape: element 0)
-            g0 = gterm.as_strided((), ()) if gterm.dim() else gterm.contiguous()
             out, truth = saved[2:4]
-            dyl = K.l1_bwd_unshuffle4(out, truth, g0, ctx.gscale) if ctx.scale == 4 else \
-                K.l1_bwd_unshuffle(out, truth, g0, ctx.scale, ctx.pcs[1].cout_pad, ctx.gscale)
+            g0, gscale = _term_gradient(gterm, ctx.gscale, out.numel())
+            dyl = K.l1_bwd_unshuffle4(out, truth, g0, gscale) if ctx.scale == 4 else \
+                K.l1_bwd_unshuffle(out, truth, g0, ctx.scale, ctx.pcs[1].cout_pad, gscale)
         dfea, *dparams = _leg_backward(ctx, fea, h, dyl)
         return (dfea, None, None, None, None, None) + tuple(dparams)
 
@@ -1030,8 +1060,8 @@ class ExitsFn(torch.autograd.Function):
             if ctx.have_dyl:
                 dyls[i] = third[i]
             else:
-                g0 = gterms[i].as_strided((), ())  # the scalar gradient arrives broadcast to the term's shape
-                dyls[i] = K.l1_bwd_unshuffle4(third[i], truth, g0, ctx.gscale)
+                g0, gscale = _term_gradient(gterms[i], ctx.gscale, third[i].numel())
+                dyls[i] = K.l1_bwd_unshuffle4(third[i], truth, g0, gscale)
         dhs = dict(zip(live, _conv_group([{"srcs": dyls[i], "wpk": legs[i][1].get()[0][1], "mask": hs[i]} for i in live], c))) if live else {}
         dfeas = [None] * M
         grads = [None] * (4 * M)
@@ -1067,12 +1097,15 @@ class LossTerm:
 class MeanTermsFn(torch.autograd.Function):
     """`loss += term` over the exits and `loss / num_modules` (models/LarvaNet.py:104-109) as one
     launch over scalars and/or partial sums (same arithmetic, same order as finishing every L1
-    separately and adding the scalars).  A finished scalar receives the gradient g / n; a
-    prescaled partial-sum term receives g itself (broadcast view, no kernel)."""
+    separately and adding the scalars).  A finished scalar receives the gradient g / n.  A prescaled partial-sum term
+    applies the 1 / n in its own backward kernel and receives, per element, g * scale (scale = 1 / numel); when the seed
+    of backward was known in the forward pass its producer has written its gradient already and ignores what arrives:
+    g itself then (broadcast view, no kernel)."""
 
     @staticmethod
     def forward(ctx, meta, *tensors):
         ctx.meta = meta
+        ctx.seeded = StepScope.seed_grad is not None
         ctx.shapes = [tuple(t.shape) for t in tensors]
         ts, scales = [t.contiguous() for t in tensors], [m[0] for m in meta]
         if (len(ts) <= 8 and DeferredWgrad.active and StepScope.depth > 0 and not StepScope.early_loss
@@ -1099,7 +1132,7 @@ class MeanTermsFn(torch.autograd.Function):
         grads = []
         for (scale, prescaled), shape in zip(ctx.meta, ctx.shapes):
             if prescaled:
-                grads.append(g.expand(shape))
+                grads.append((g if ctx.seeded else g * scale).expand(shape))
             else:
                 gm = g / n if gm is None else gm
                 grads.append(gm if scale == 1.0 else gm * scale)

@@ -21,7 +21,7 @@ import torch.nn as nn
 from .. import dist as ldist
 from .. import kernels as K
 from ..autograd import (BodyFn, DeferredWgrad, DualChain, ExitFn, ExitsFn, GradBucket, HeadFn, L1LossFn, LegFn, LossTerm, PackedConv, PaddedWidth, mean_of_terms,
-                        StepScope, pack_all)
+                        StepScope, pack_all, refuse_grad_of)
 from ..autograd import step_prologue as autograd_step_prologue
 from ..captured_step import CapturedStep, LossCopy
 from ..infer_graphs import GraphTable
@@ -85,6 +85,7 @@ class L1Loss(nn.Module):
     """nn.L1Loss() replacement (models/LarvaNet.py:85) backed by the fused HIP reduction."""
 
     def forward(self, output, target):
+        refuse_grad_of(target, "the truth (the loss's target)", "L1Loss")
         _require_hip(output)
         return L1LossFn.apply(output, target)
 
@@ -113,6 +114,7 @@ class LarvaHead(nn.Module):
         self._pc = PackedConv(self.feature_extraction.weight, self.feature_extraction.bias, cin_pad=16)
 
     def forward(self, x, x16=None):
+        refuse_grad_of(x, "the input image", "LarvaHead")
         _require_hip(x)
         c = self.feature_extraction
         self._pc.refresh()
@@ -138,6 +140,7 @@ class LarvaLeg(nn.Module):
     merges = False   # (LarvaNetModule.forward: this end reads the last body's output, not every body's)
 
     def forward(self, fea, base):
+        refuse_grad_of(base, "the base image", "LarvaLeg")
         _require_hip(fea)
         return run_leg(self, fea, base)
 
@@ -147,6 +150,9 @@ def run_leg(end, fea, base, truth=None, divisor=None):
     PixelShuffle(scale) -> + base to `fea`: the image (LegFn) or, given the truth, one fused training exit (ExitFn) ->
     (image, loss term).  An end that merges (the tail) is handed every body's output and runs its merge conv on them
     first, after the refresh."""
+    refuse_grad_of(base, "the base image", type(end).__name__)
+    if truth is not None:
+        refuse_grad_of(truth, "the truth", "an exit of " + type(end).__name__)
     for pc in end._pcs:
         pc.refresh()
     if end.merges:
@@ -256,6 +262,7 @@ class LarvaNetModule(nn.Module):
 
     def base(self, x):
         """F.interpolate(x, scale_factor=scale, mode=args.interpolate, align_corners=False) (models/LarvaNet.py:283-285)."""
+        refuse_grad_of(x, "the input image", "the base interpolation")
         _require_hip(x)
         if self.interpolate not in SUPPORTED_INTERPOLATE:   # (parse_args already refuses it)
             raise ValueError("larvanet_amd: --interpolate=%s has no HIP kernel; supported: %s"
@@ -332,6 +339,7 @@ class LarvaNetModule(nn.Module):
             return out
 
     def forward(self, x):
+        refuse_grad_of(x, "the input image", "the network")
         bodies, end = self.route()
         base = self.base(x)
         if end is None:
@@ -563,6 +571,8 @@ class LarvaNet(InferenceMixin, BaseModel):
 
     def _all_exits(self, feas, base, truth_tensor):
         """(last exit's image, [LossTerm per exit]) from the body outputs, in one ExitsFn node."""
+        refuse_grad_of(base, "the base image", "the batched exits")
+        refuse_grad_of(truth_tensor, "the truth", "the batched exits")
         legs, params = [], []
         for i in range(len(feas)):
             leg = getattr(self.model, "body_%d" % i).leg

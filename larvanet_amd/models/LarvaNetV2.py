@@ -11,7 +11,7 @@ state_dict adds tail.merge_conv.{weight,bias} and tail.recon_block.{0,2}.{weight
 import torch
 import torch.nn as nn
 
-from ..autograd import DualChain, MergeFn, PackedConv, mean_of_terms
+from ..autograd import DualChain, MergeFn, PackedConv, mean_of_terms, refuse_grad_of
 from . import LarvaNet as V1
 from .LarvaNet import NUM_FILTERS, _conv, _require_hip, init_conv, run_leg
 
@@ -47,6 +47,7 @@ class LarvaTail(nn.Module):
         return MergeFn.apply(self._pc, m.weight, m.bias, *[f.contiguous() for f in features])
 
     def forward(self, features, base):
+        refuse_grad_of(base, "the base image", "LarvaTail")
         _require_hip(features[0])
         self._pc.refresh()
         return run_leg(self, features, base)

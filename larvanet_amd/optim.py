@@ -38,7 +38,11 @@ class FlatAdamW(torch.optim.AdamW):
         self.mean_scale = 1.0   # (not "grad_scale": torch.optim reserves that attribute for AMP) gradients are multiplied by this inside the step (1/world_size: mean over ranks)
 
     def _flat_ok(self):
-        if self._flat_p is None or self._bucket is None or not self._bucket.intact():
+        if self._flat_p is None or self._bucket is None:
+            return False
+        # every step asks only whether the .grad views are still attached (GradBucket.views_attached): a parameter frozen
+        # since has made the plugin drop them before the step gets here.  A bucket that only knows intact() is asked that.
+        if not getattr(self._bucket, "views_attached", self._bucket.intact)():
             return False
         off = 0
         base = self._flat_p.data_ptr()

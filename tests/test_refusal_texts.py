@@ -1,7 +1,8 @@
 """Every refusal of the image entry points and of the three streams, word for word: exception type and full message are
 literals recorded before the checks were folded into shared ones, so a shared check cannot change what a caller reads or
 which of two refusals wins.  Host only: nothing here launches; the plugin is told it sits on the CPU, so a call whose
-arguments pass ends in the "only runs on a HIP device" refusal wherever the suite runs."""
+arguments pass ends in the "only runs on a HIP device" refusal wherever the suite runs.  Likewise the refusals of the
+autograd modules for an input whose gradient they do not compute (the image, a leg's base, a loss's truth)."""
 import gc
 
 import numpy as np
@@ -232,12 +233,45 @@ def _cases(m, se):
         ("stream frame: wrong rank", lambda: P._check_frame(frame.reshape(9, 8), NBYTES, W, H)),
         ("stream frame: wrong dtype beats wrong size", lambda: P._check_frame(frame[:-1].astype(f32), NBYTES, W, H)),
     ]
+    # ---- inputs whose gradient the autograd nodes do not compute: refused where torch would return one, never a silent
+    # None; under no_grad the same tensors pass (and end, on the host, in the no-CPU-fallback refusal)
+    from larvanet_amd.models import LarvaNet as L1, LarvaNetV2 as L2
+    net, leg, tail = m.model, m.model.body_0.leg, L2.LarvaTail(2)
+    xg = torch.zeros(1, 3, H, W, requires_grad=True)
+    fea, hr = torch.zeros(1, 48, H, W), torch.zeros(1, 3, 4 * H, 4 * W)
+    hrg = torch.zeros(1, 3, 4 * H, 4 * W, requires_grad=True)
+
+    def no_grad(call):
+        def run():
+            with torch.no_grad():
+                return call()
+        return run
+
+    needs = [
+        ("head: the image needs a gradient", lambda: net.head(xg)),
+        ("network: the image needs a gradient", lambda: net(xg)),
+        ("all exits: the image needs a gradient", lambda: net.forward_exits(xg)),
+        ("base: the image needs a gradient", lambda: net.base(xg)),
+        ("leg: the base needs a gradient", lambda: leg(fea, hrg)),
+        ("tail: the base needs a gradient", lambda: tail([fea, fea], hrg)),
+        ("run_leg: the base needs a gradient", lambda: L1.run_leg(leg, fea, hrg, hr, 2)),
+        ("run_leg: the truth needs a gradient", lambda: L1.run_leg(leg, fea, hr, hrg, 2)),
+        ("run_leg: the base beats the truth", lambda: L1.run_leg(tail, [fea, fea], hrg, hrg)),
+        ("batched exits: the base needs a gradient", lambda: m._all_exits([fea, fea], hrg, hr)),
+        ("batched exits: the truth needs a gradient", lambda: m._all_exits([fea, fea], hr, hrg)),
+        ("L1Loss: the truth needs a gradient", lambda: L1.L1Loss()(hr, hrg)),
+    ]
+    cases += needs
+    # (run_leg and the batched exits are internal: they leave the device check to the modules that call them)
+    cases += [(label + ", under no_grad", no_grad(call)) for label, call in needs
+              if not label.startswith(("run_leg", "batched exits"))]
     return cases
 
 
 V, T, R = ValueError, TypeError, RuntimeError
 P_ = "larvanet_amd: "
 NO_HIP = (R, P_ + "the network only runs on a HIP device (MI355X); got a cpu tensor and there is no CPU fallback")
+NO_GRAD = P_ + "the gradient of %s is not computed by %s; detach() it, or call under torch.no_grad()"
 RATIO = (V, P_ + "resizing shrinks an axis by at most 4, got 24 x 32 -> 5 x 32 (height x width)")
 NOT_A_PAIR = (T, P_ + "output_size is (height, width) or None, got (5,)")
 ENSEMBLE = (V, P_ + "--self_ensemble together with all-exit inference is not supported; run one of the two")
@@ -491,7 +525,21 @@ EXPECTED = {
     "stream frame: wrong size": (V, P_ + "an I420 frame of 8 x 6 is a flat buffer of 72 bytes, got shape (71,)"),
     "stream frame: wrong rank": (V, P_ + "an I420 frame of 8 x 6 is a flat buffer of 72 bytes, got shape (9, 8)"),
     "stream frame: wrong dtype beats wrong size": (T, P_ + "upscale_yuv_stream takes uint8 numpy frames, got float32"),
+    "head: the image needs a gradient": (R, NO_GRAD % ("the input image", "LarvaHead")),
+    "network: the image needs a gradient": (R, NO_GRAD % ("the input image", "the network")),
+    "all exits: the image needs a gradient": (R, NO_GRAD % ("the input image", "the base interpolation")),
+    "base: the image needs a gradient": (R, NO_GRAD % ("the input image", "the base interpolation")),
+    "leg: the base needs a gradient": (R, NO_GRAD % ("the base image", "LarvaLeg")),
+    "tail: the base needs a gradient": (R, NO_GRAD % ("the base image", "LarvaTail")),
+    "run_leg: the base needs a gradient": (R, NO_GRAD % ("the base image", "LarvaLeg")),
+    "run_leg: the truth needs a gradient": (R, NO_GRAD % ("the truth", "an exit of LarvaLeg")),
+    "run_leg: the base beats the truth": (R, NO_GRAD % ("the base image", "LarvaTail")),
+    "batched exits: the base needs a gradient": (R, NO_GRAD % ("the base image", "the batched exits")),
+    "batched exits: the truth needs a gradient": (R, NO_GRAD % ("the truth", "the batched exits")),
+    "L1Loss: the truth needs a gradient": (R, NO_GRAD % ("the truth (the loss's target)", "L1Loss")),
 }
+EXPECTED.update({label + ", under no_grad": NO_HIP for label in list(EXPECTED)
+                 if label.endswith("needs a gradient") and not label.startswith(("run_leg", "batched exits"))})
 
 
 def _refusal(call):
