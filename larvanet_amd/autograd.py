@@ -343,7 +343,7 @@ def step_prologue(pcs, x):
     N, C, H, W = (int(v) for v in x.shape)
     if len(jobs) > 64 or C > 16 or PaddedWidth.current is not None or not x.is_contiguous():
         return None
-    x16 = StepScope.padded_input((N, 16, H, W), x.device)
+    x16 = StepScope.padded_input((N, 16, H, W), x.device, C, W)
     base = torch.empty((N, C, 4 * H, 4 * W), device=x.device, dtype=torch.float32)
     with torch.no_grad():
         K.step_prologue(jobs, x.detach(), x16, base)
@@ -569,17 +569,23 @@ class StepScope:
     early_loss = False
 
     @classmethod
-    def padded_input(cls, shape, device):
-        """Zero tensor for the head's channel-padded input.  Inside a scope it is a cached buffer
-        (zeroed once; the caller overwrites the same sub-block every step), elsewhere a fresh one."""
+    def padded_input(cls, shape, device, channels, width):
+        """Zero tensor of `shape` = (N, 16, H, P) for the head's padded input, of which the caller writes the block
+        [:, :channels, :, :width] and nothing else.  Inside a scope it is a cached buffer (zeroed once; every caller
+        with this key overwrites the same block every step), elsewhere a fresh one.  The written block is part of the
+        key: under PaddedWidth the widths 21, 22 and 23 all have P = 24, and the buffer of one would hand the next a
+        pad column [width, P) that still holds the wider image's pixels, which the conv reads as its zero padding."""
         if cls.depth == 0:
             return torch.zeros(shape, device=device, dtype=torch.float32)
-        key = (tuple(shape), str(device))
+        key = (tuple(shape), str(device), int(channels), int(width))
         buf = cls._padded.get(key)
         if buf is None:
-            # Never evicted: captured graphs (the training step, up to four inference shapes per model) bake this
-            # buffer's address in, and a freed buffer's memory would be handed to somebody else.  Scoped shapes are
-            # the training batch shapes and the captured inference shapes -- a handful of N x 16 x H x W buffers.
+            # Never evicted: captured graphs (the training step, up to four inference shapes per table and model) bake
+            # this buffer's address in, and a freed buffer's memory would be handed to somebody else.  Scoped shapes
+            # are the training batch shapes and the captured inference shapes -- a handful of N x 16 x H x P buffers,
+            # one per written block.  Captures of one key (two plugins, or the training step and the inference
+            # forward of its batch shape) share the buffer: each rewrites the whole block before it reads it, and
+            # they run one after the other on a stream (tests/test_interleaved_shapes.py).
             buf = cls._padded[key] = torch.zeros(shape, device=device, dtype=torch.float32)
         return buf
 
@@ -716,7 +722,7 @@ class HeadFn(torch.autograd.Function):
         if x16 is not None:      # prepared by the step's prologue launch (step_prologue)
             pass
         elif training or not use_direct:
-            x16 = StepScope.padded_input((N, 16, H, P), x.device)  # channels C..15 / columns W..P-1 stay zero
+            x16 = StepScope.padded_input((N, 16, H, P), x.device, C, W)  # channels C..15 / columns W..P-1 stay zero
             x16[:, :C, :, :W] = x
         if use_direct:
             out = K.head_conv3_direct(x, weight.detach(), bias.detach(), pitch=P)
