@@ -2,6 +2,7 @@
 between them, so forward + backward are captured once per (batch shape, early-loss mode) and replayed.  The plugin
 (models/LarvaNet.py) holds at most one CapturedStep and replaces it only by another that was captured whole."""
 import contextlib
+import gc
 
 import torch
 
@@ -47,6 +48,7 @@ class CapturedStep:
                 DeferredWgrad.flush_late()
         torch.cuda.current_stream().wait_stream(side)
         plugin._zero_grad()
+        gc.collect()   # (a dropped plugin's graphs must not be freed while a capture is open: inference._capture_infer)
         graph = torch.cuda.CUDAGraph()
         back = torch.cuda.CUDAGraph() if mode == "split" else None
         # thread_local: a process-group watchdog thread must not abort the capture

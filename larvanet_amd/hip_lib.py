@@ -1,182 +1,63 @@
 """ctypes binding of liblarva_hip.so (the C ABI declared in include/larva_hip.h).
 
+The header is the only place an entry point's types are written down: SIGNATURES is parsed from it at import
+(parse_header), so a new entry point needs its declaration, its .hip definition and its wrapper in kernels.py, nothing
+here.  A declaration the parser cannot type, a missing header and a symbol the library does not export all raise.
+
 There is no fallback: if the library is missing or a call fails, a RuntimeError is raised.
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "liblarva_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "larva_hip.h")
 
-_c_float_p = ctypes.c_void_p  # device pointers travel as integers
-_c_pp = ctypes.POINTER(ctypes.c_void_p)
-_c_int_p = ctypes.POINTER(ctypes.c_int)
+_SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "float": ctypes.c_float, "double": ctypes.c_double,
+            "long long": ctypes.c_longlong}
 
-# name -> (restype, argtypes); mirrors include/larva_hip.h one to one
-SIGNATURES = {
-    "larva_abi_version": (ctypes.c_int, []),
-    "larva_error_string": (ctypes.c_char_p, [ctypes.c_int]),
-    "larva_packed_weight_floats": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
-    "larva_pack_weights": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int,
-                                          ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_pack_weights_batch": (ctypes.c_int, [_c_pp, _c_pp, _c_pp, _c_int_p, _c_int_p, _c_int_p, _c_int_p,
-                                                ctypes.c_int, ctypes.c_void_p]),
-    "larva_step_prologue": (ctypes.c_int, [_c_pp, _c_pp, _c_pp, _c_int_p, _c_int_p, _c_int_p, _c_int_p, ctypes.c_int,
-                                           _c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                           ctypes.c_int, ctypes.c_void_p]),
-    "larva_conv3x3_fwd": (ctypes.c_int, [_c_pp, ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p,
-                                         _c_float_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p,
-                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                         ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_conv3x3_fwd_pitched": (ctypes.c_int, [_c_pp, ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p,
-                                                 _c_float_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p,
-                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_conv3x3_fwd_batch": (ctypes.c_int, [ctypes.c_int, _c_pp, ctypes.c_int, ctypes.c_int, _c_pp, _c_pp, _c_pp, _c_pp,
-                                               _c_pp, _c_pp, _c_pp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_conv3x3_fwd_tiled": (ctypes.c_int, [_c_pp, ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p,
-                                               _c_float_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p,
-                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_conv3x3_fwd_strips": (ctypes.c_int, [_c_pp, ctypes.c_int, ctypes.c_int, _c_float_p, _c_float_p,
-                                                _c_float_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p,
-                                                ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                                                ctypes.POINTER(ctypes.c_uint), ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_head_conv3_direct": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int,
-                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_exit_l1_partials": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "larva_conv3x3_exit_l1_batch": (ctypes.c_int, [ctypes.c_int, _c_pp, ctypes.c_int, ctypes.c_int, _c_pp, _c_pp, _c_pp, _c_pp,
-                                                   _c_pp, _c_pp, _c_pp, ctypes.c_float, ctypes.c_int, ctypes.c_int,
-                                                   ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_strip_tile_table": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint),
-                                              ctypes.c_int]),
-    "larva_wgrad_partial_floats": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "larva_conv3x3_wgrad": (ctypes.c_int, [_c_pp, _c_pp, _c_pp, _c_pp, _c_pp, _c_int_p, _c_int_p, _c_int_p,
-                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_conv3x3_wgrad_partial": (ctypes.c_int, [_c_pp, _c_pp, _c_pp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                   ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                   _c_int_p, ctypes.c_void_p]),
-    "larva_wgrad_flat_head_splits": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "larva_conv3x3_wgrad_partial_flat_head": (ctypes.c_int, [_c_pp, _c_pp, _c_pp, ctypes.c_int, _c_float_p, _c_float_p,
-                                                             _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                             ctypes.c_int, _c_int_p, _c_int_p, ctypes.c_void_p]),
-    "larva_wgrad_flat_max_splits": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "larva_conv3x3_wgrad_partial_flat": (ctypes.c_int, [_c_pp, _c_pp, _c_pp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                        _c_int_p, ctypes.c_void_p]),
-    "larva_wgrad_reduce": (ctypes.c_int, [_c_pp, _c_pp, _c_pp, _c_int_p, _c_int_p, _c_int_p, _c_int_p, _c_int_p,
-                                          _c_int_p, ctypes.c_int, ctypes.c_void_p]),
-    "larva_wgrad_reduce_with_loss": (ctypes.c_int, [_c_pp, _c_pp, _c_pp, _c_int_p, _c_int_p, _c_int_p, _c_int_p, _c_int_p,
-                                                    _c_int_p, ctypes.c_int, _c_pp, _c_int_p, _c_float_p, ctypes.c_int,
-                                                    ctypes.c_float, _c_float_p, ctypes.c_void_p]),
-    "larva_adamw_step_host_copy": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, _c_float_p, ctypes.c_int,
-                                                  ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                                  ctypes.c_double, ctypes.c_float, ctypes.c_longlong, _c_float_p, _c_float_p,
-                                                  ctypes.c_void_p]),
-    "larva_upsample4_fwd": (ctypes.c_int, [_c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                           ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_bicubic4_fwd": (ctypes.c_int, [_c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                          ctypes.c_int, ctypes.c_void_p]),
-    "larva_l1_workspace_floats": (ctypes.c_int, []),
-    "larva_l1_fwd": (ctypes.c_int, [_c_float_p, _c_float_p, ctypes.c_longlong, _c_float_p, _c_float_p,
-                                    ctypes.c_void_p]),
-    "larva_l1_bwd": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, ctypes.c_longlong, _c_float_p,
-                                    ctypes.c_void_p]),
-    "larva_l1_bwd_unshuffle4": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, ctypes.c_float, _c_float_p,
-                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_l1_partial": (ctypes.c_int, [_c_float_p, _c_float_p, ctypes.c_longlong, _c_float_p, _c_int_p,
-                                        ctypes.c_void_p]),
-    "larva_l1_partial_grad": (ctypes.c_int, [_c_float_p, _c_float_p, ctypes.c_float, ctypes.c_float, _c_float_p,
-                                             _c_int_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                             ctypes.c_int, ctypes.c_void_p]),
-    "larva_l1_partial_grad_batch": (ctypes.c_int, [_c_pp, _c_float_p, ctypes.c_int, ctypes.c_float, ctypes.c_float, _c_pp,
-                                                   _c_int_p, _c_pp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                   ctypes.c_int, ctypes.c_void_p]),
-    "larva_loss_from_partials_to_host": (ctypes.c_int, [_c_pp, _c_int_p, _c_float_p, ctypes.c_int, ctypes.c_float,
-                                                        _c_float_p, _c_float_p, ctypes.c_void_p]),
-    "larva_loss_from_partials_to_host_seq": (ctypes.c_int, [_c_pp, _c_int_p, _c_float_p, ctypes.c_int, ctypes.c_float,
-                                                            _c_float_p, _c_float_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "larva_host_cell_alloc": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p)]),
-    "larva_host_cell_free": (ctypes.c_int, [_c_float_p]),
-    "larva_loss_from_partials": (ctypes.c_int, [_c_pp, _c_int_p, _c_float_p, ctypes.c_int, ctypes.c_float,
-                                                _c_float_p, ctypes.c_void_p]),
-    "larva_sum_scalars": (ctypes.c_int, [_c_pp, ctypes.c_int, ctypes.c_float, _c_float_p, ctypes.c_void_p]),
-    "larva_upsample_fwd": (ctypes.c_int, [_c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                          ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_pixel_shuffle_base": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_pixel_unshuffle": (ctypes.c_int, [_c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                             ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_l1_bwd_unshuffle": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, ctypes.c_float, _c_float_p, ctypes.c_int,
-                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                              ctypes.c_void_p]),
-    "larva_shuffle_l1_partial_grad": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, ctypes.c_float, ctypes.c_float,
-                                                     _c_float_p, _c_int_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int,
-                                                     ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_pixel_unshuffle4": (ctypes.c_int, [_c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int,
-                                              ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_wgrad_cu_share": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
-    "larva_adamw_step_host": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, _c_float_p, ctypes.c_int,
-                                             ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                             ctypes.c_double, ctypes.c_float, ctypes.c_longlong, ctypes.c_void_p]),
-    "larva_gather_patches": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                            _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_sqerr_u8": (ctypes.c_int, [_c_float_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                      ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
-    "larva_adamw_step": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p,
-                                        ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                        ctypes.c_float, ctypes.c_longlong, ctypes.c_void_p]),
-    "larva_f16_packed_weight_halves": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]),
-    "larva_f16_pack_weights": (ctypes.c_int, [_c_float_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_f16_head": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                      ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_f16_conv3x3": (ctypes.c_int, [_c_pp, ctypes.c_int, ctypes.c_void_p, _c_float_p, ctypes.c_void_p, ctypes.c_void_p,
-                                         ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                         ctypes.c_int, ctypes.c_void_p]),
-    "larva_f16_conv3x3_shuffle_base": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p, _c_float_p,
-                                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_f16_conv3x3_shuffle_base_u8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p,
-                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                                         ctypes.c_int, ctypes.c_void_p]),
-    "larva_f16_conv3x3_jobs": (ctypes.c_int, [ctypes.c_int, _c_pp, _c_pp, _c_pp, ctypes.c_int, _c_pp, ctypes.c_void_p,
-                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_f16_conv3x3_shuffle_base_jobs": (ctypes.c_int, [ctypes.c_int, _c_pp, _c_pp, _c_pp, _c_float_p, _c_pp, _c_pp,
-                                                           ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                           ctypes.c_void_p]),
-    "larva_u8_hwc_to_f32_chw": (ctypes.c_int, [ctypes.c_void_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                               ctypes.c_void_p]),
-    "larva_f32_chw_to_u8_hwc": (ctypes.c_int, [_c_float_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                               ctypes.c_void_p]),
-    "larva_u8_metrics_workspace_bytes": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "larva_u8_metrics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
-                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "larva_dihedral_inputs_u8": (ctypes.c_int, [ctypes.c_void_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int,
-                                                ctypes.c_int, ctypes.c_void_p]),
-    "larva_dihedral_inputs_f32": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int,
-                                                 ctypes.c_int, ctypes.c_void_p]),
-    "larva_dihedral_mean": (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                           ctypes.c_int, ctypes.c_void_p]),
-    "larva_bicubic_down_u8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int,
-                                             ctypes.c_void_p, ctypes.c_void_p]),
-    "larva_bicubic_down_u8_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                                   ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
-    "larva_i420_to_rgb_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, _c_float_p, ctypes.c_int, ctypes.c_int,
-                                             ctypes.c_int, _c_int_p, ctypes.c_void_p]),
-    "larva_rgb_u8_to_i420": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
-                                            ctypes.c_int, _c_int_p, ctypes.c_void_p]),
-    "larva_resize_u8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                       ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
-    "larva_rgba_u8_split_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_float_p, ctypes.c_int, ctypes.c_int,
-                                               ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    "larva_rgb_u8_merge_rgba": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                               ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-}
+
+def _ctype(text, decl, named):
+    """One C type of a declaration (`named`: a parameter, whose name is dropped) -> its ctypes type."""
+    stars = text.count("*")
+    words = re.sub(r"\bconst\b|\*", " ", text).split()
+    if named and len(words) > 1:
+        words.pop()
+    base = " ".join(words)
+    if stars:
+        # device pointers travel as integers; host arrays, byref() and None pass as c_void_p too
+        return ctypes.c_char_p if base == "char" and not named else ctypes.c_void_p
+    if base == "void" and not named:
+        return None
+    if base not in _SCALARS:
+        raise RuntimeError("larvanet_amd: no ctypes type for `%s` in the declaration `%s`" % (text.strip(), decl))
+    return _SCALARS[base]
+
+
+def parse_header(path):
+    """name -> (restype, [argtypes]) of every `ret larva_name(args);` a C header declares.  Comments, preprocessor lines,
+    `typedef struct` blocks and the extern "C" braces are stepped over; anything else raises: nothing is skipped and
+    nothing gets a default type."""
+    if not os.path.exists(path):
+        raise RuntimeError("larvanet_amd: %s is missing: the ctypes binding is derived from it" % path)
+    text = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
+    text = re.sub(r"//[^\n]*|^[ \t]*#.*$", " ", text, flags=re.M)
+    text = re.sub(r"\btypedef\s+struct\b[^{;]*\{.*?\}[^;]*;", " ", text, flags=re.S)
+    text = re.sub(r'\bextern\s+"C"\s*\{|\}', " ", text)
+    signatures = {}
+    for decl in (" ".join(d.split()) for d in text.split(";")):
+        if not decl:
+            continue
+        m = re.fullmatch(r"(.+?)\b(larva_\w+) ?\((.*)\)", decl)
+        if m is None or m.group(2) in signatures:
+            raise RuntimeError("larvanet_amd: %s: cannot bind `%s`" % (path, decl))
+        args = [] if m.group(3).strip() in ("", "void") else m.group(3).split(",")
+        signatures[m.group(2)] = (_ctype(m.group(1), decl, False), [_ctype(a, decl, True) for a in args])
+    return signatures
+
+
+SIGNATURES = parse_header(HEADER_PATH)   # name -> (restype, argtypes)
 
 _lib = None
 

@@ -4,6 +4,8 @@ checks and its device-side composer.  A mixin without state of its own: models/L
 of BaseModel and sets, in __init__ / prepare(), what it reads -- model, precision, device, scale, args, use_hip_graph,
 strict_graph, dual_chain, batch_exit_legs and the four graph tables.  pipeline.py's streams run the same composers with
 _infer_u8_images as the forward and a staging slot's buffer as the destination."""
+import gc
+
 import numpy as np
 import torch
 
@@ -85,6 +87,9 @@ class InferenceMixin:
                     with self._infer_scope():
                         self._forward_nograd(static_x, *form, exits=form.exits)
             torch.cuda.current_stream().wait_stream(side)
+            # A plugin holds its captured graphs in reference cycles: one that was dropped lives until the collector
+            # runs, and a graph freed while this capture is open calls into the HIP runtime and aborts the process.
+            gc.collect()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
                 with self._infer_scope():

@@ -46,6 +46,35 @@ def _opt(t, name, shape):
     return None if t is None else _chk(t, name, shape)
 
 
+def _out(out, shape, device, dtype=torch.float32, last=None, name="out"):
+    """The caller's `out`, checked like any operand, or a new tensor of that shape."""
+    if out is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    _chk_tensor(out, name, shape, dtype, last)
+    return out
+
+
+def _src_list(srcs):
+    return [srcs] if isinstance(srcs, torch.Tensor) else list(srcs)
+
+
+def _try_launch(name, *args):
+    """_launch, but hipErrorNotSupported (the entry point does not take these operands, e.g. unaligned ones; nothing was
+    launched) -> False instead of raising."""
+    code = getattr(hip_lib.load(), name)(*args, _stream())
+    if code == 801:
+        return False
+    hip_lib.check(code, name)
+    return True
+
+
+def _launch(name, *args, stream=True):
+    """Entry point `name` of the library on the current stream (stream=False: it takes none), its code checked.  The
+    entry point is looked up on every call: tests put spies on the library object."""
+    fn = getattr(hip_lib.load(), name)
+    hip_lib.check(fn(*args, _stream()) if stream else fn(*args), name)
+
+
 def packed_weight_floats(cout, cin):
     return int(hip_lib.load().larva_packed_weight_floats(cout, cin))
 
@@ -56,7 +85,6 @@ def pack_weights(w, cin_off=0, cin=None, cin_pad=None, want_bwd=True):
     Packs the input-channel slice [cin_off, cin_off+cin) (default: to the end).  cin_pad pads
     with zero channels up to that kernel channel count (head conv: 3 -> 16); padding is only
     meaningful when the slice ends at cin_total."""
-    lib = hip_lib.load()
     _chk(w, "w")
     if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
         raise RuntimeError("larvanet_amd: only [cout][cin][3][3] weights are supported")
@@ -71,9 +99,8 @@ def pack_weights(w, cin_off=0, cin=None, cin_pad=None, want_bwd=True):
         raise RuntimeError("larvanet_amd: channel counts must be multiples of 8 (cout=%d cin=%d)" % (cout, cin_k))
     fwd = torch.empty(packed_weight_floats(cout, cin_k), device=w.device, dtype=torch.float32)
     bwd = torch.empty(packed_weight_floats(cin_k, cout), device=w.device, dtype=torch.float32) if want_bwd else None
-    code = lib.larva_pack_weights(w.data_ptr(), fwd.data_ptr(), bwd.data_ptr() if want_bwd else None,
-                                  cout, cin_k, cin_total, cin_off, _stream())
-    hip_lib.check(code, "larva_pack_weights")
+    _launch("larva_pack_weights", w.data_ptr(), fwd.data_ptr(), bwd.data_ptr() if want_bwd else None,
+            cout, cin_k, cin_total, cin_off)
     return fwd, bwd
 
 
@@ -100,10 +127,8 @@ def _pack_job_args(jobs):
 def pack_weights_batch(jobs):
     """jobs: list of (w, fwd_buf, bwd_buf or None, cout, cin_k, cin_off): packs every weight
     (slice) into its persistent kernel-layout buffers with one launch per 64 jobs."""
-    lib = hip_lib.load()
     for i in range(0, len(jobs), 64):
-        code = lib.larva_pack_weights_batch(*_pack_job_args(jobs[i:i + 64]), _stream())
-        hip_lib.check(code, "larva_pack_weights_batch")
+        _launch("larva_pack_weights_batch", *_pack_job_args(jobs[i:i + 64]))
 
 
 _STRIP_TABLES = {}
@@ -116,10 +141,9 @@ def strip_tile_table(H, P, device, phase=0):
     key = (int(H), int(P), str(device), int(phase))
     hit = _STRIP_TABLES.get(key)
     if hit is None:
-        lib = hip_lib.load()
         cap = 4 * ((H + 3) // 4) * ((P + 15) // 16) + 16
         buf = (ctypes.c_uint * cap)()
-        n = int(lib.larva_strip_tile_table(int(H), int(P), int(phase), buf, cap))
+        n = int(hip_lib.load().larva_strip_tile_table(int(H), int(P), int(phase), buf, cap))
         if n <= 0 or n > cap:
             hit = False
         else:
@@ -136,15 +160,13 @@ def strip_tile_table(H, P, device, phase=0):
 
 def step_prologue(jobs, x, x16, base):
     """pack_weights_batch(jobs) (<= 64 jobs) + x16[:, :C] = x + base = bicubic4(x) in one launch."""
-    lib = hip_lib.load()
     if len(jobs) > 64:
         raise RuntimeError("larvanet_amd: at most 64 pack jobs per prologue launch")
     N, C, H, W = (int(v) for v in x.shape)
     _chk(x, "x")
     _chk(x16, "x16", (N, 16, H, W))
     _chk(base, "base", (N, C, 4 * H, 4 * W))
-    code = lib.larva_step_prologue(*_pack_job_args(jobs), x.data_ptr(), x16.data_ptr(), base.data_ptr(), N, C, H, W, _stream())
-    hip_lib.check(code, "larva_step_prologue")
+    _launch("larva_step_prologue", *_pack_job_args(jobs), x.data_ptr(), x16.data_ptr(), base.data_ptr(), N, C, H, W)
 
 
 def conv3x3(srcs, wpk, cout, bias=None, relu=False, mask=None, res0=None, res1=None,
@@ -167,9 +189,7 @@ def conv3x3(srcs, wpk, cout, bias=None, relu=False, mask=None, res0=None, res1=N
     Views: srcs, wpk, mask, res0, res1 and a shuffle=False out may start on any 4-byte boundary (off the 16-byte grid the
     register-staged kernel runs: same results; strips then fall back to the regular tiles, tile_rows=4 raises); with
     shuffle=True `out` and `base` must be 16-byte aligned (RuntimeError otherwise, nothing is written)."""
-    lib = hip_lib.load()
-    if isinstance(srcs, torch.Tensor):
-        srcs = [srcs]
+    srcs = _src_list(srcs)
     if not 1 <= len(srcs) <= 8:
         raise RuntimeError("larvanet_amd: 1..8 source tensors")
     if cout not in _SUPPORTED_COUT:
@@ -185,9 +205,7 @@ def conv3x3(srcs, wpk, cout, bias=None, relu=False, mask=None, res0=None, res1=N
     _chk(wpk, "wpk", (packed_weight_floats(cout, cin),))
     full = (N, cout, H, P)
     hr = (N, cout // 16, 4 * H, 4 * W)
-    if out is None:
-        out = torch.empty(hr if shuffle else full, device=srcs[0].device, dtype=torch.float32)
-    _chk(out, "out", hr if shuffle else full)
+    out = _out(out, hr if shuffle else full, srcs[0].device)
     lo, hi = (0, N) if images is None else (int(images[0]), int(images[1]))
     if not 0 <= lo < hi <= N:
         raise RuntimeError("larvanet_amd: image range [%d, %d) outside the batch of %d" % (lo, hi, N))
@@ -204,16 +222,14 @@ def conv3x3(srcs, wpk, cout, bias=None, relu=False, mask=None, res0=None, res1=N
             hi - lo, cout, H, W, P, 1 if relu else 0, 1 if shuffle else 0)
     if strips and cout in (48, 32, 64):
         tab = strip_tile_table(H, P, out.device, phase=1 if strips == 2 else 0)
-        if tab is not None:
-            code = lib.larva_conv3x3_fwd_strips(*args, tab[0].data_ptr(), tab[2], tab[1], 1 if plain_stores else 0, _stream())
-            if code != 801:   # hipErrorNotSupported: unaligned operands -> the regular tiles below
-                hip_lib.check(code, "larva_conv3x3_fwd_strips")
-                return out
+        # (refused: unaligned operands -> the regular tiles below)
+        if tab is not None and _try_launch("larva_conv3x3_fwd_strips", *args, tab[0].data_ptr(), tab[2], tab[1],
+                                           1 if plain_stores else 0):
+            return out
     if tile_rows:
-        code = lib.larva_conv3x3_fwd_tiled(*args, int(tile_rows), _stream())
+        _launch("larva_conv3x3_fwd_tiled", *args, int(tile_rows))
     else:
-        code = lib.larva_conv3x3_fwd_pitched(*args, _stream())
-    hip_lib.check(code, "larva_conv3x3_fwd")
+        _launch("larva_conv3x3_fwd_pitched", *args)
     return out
 
 
@@ -223,13 +239,9 @@ def conv3x3_batch(jobs, cout, relu=False, shuffle=False, logical_w=None, outs=No
     res0, res1, base -- a fusion operand is given by every job or by none.  Returns the outputs
     (outs: the caller's tensors, one per job, e.g. slices of one buffer).
     Falls back to one launch per job where the 16-byte staging path does not apply."""
-    lib = hip_lib.load()
     if not 2 <= len(jobs) <= 4:
         raise RuntimeError("larvanet_amd: 2..4 conv jobs per batched launch")
-    norm = []
-    for j in jobs:
-        srcs = j["srcs"]
-        norm.append(dict(j, srcs=[srcs] if isinstance(srcs, torch.Tensor) else list(srcs)))
+    norm = [dict(j, srcs=_src_list(j["srcs"])) for j in jobs]
     n_src = len(norm[0]["srcs"])
     N, cps, H, P = (int(v) for v in norm[0]["srcs"][0].shape)
     W = P if logical_w is None else int(logical_w)
@@ -251,11 +263,7 @@ def conv3x3_batch(jobs, cout, relu=False, shuffle=False, logical_w=None, outs=No
         for k, shape in (("bias", (cout,)), ("res0", full), ("res1", full), ("mask", full), ("base", hr)):
             if used[k]:
                 cols[k].append(_chk(j[k], k, shape))
-        if given is None:
-            outs.append(torch.empty(hr if shuffle else full, device=j["srcs"][0].device, dtype=torch.float32))
-        else:
-            _chk(given[n_job], "out", hr if shuffle else full)
-            outs.append(given[n_job])
+        outs.append(_out(None if given is None else given[n_job], hr if shuffle else full, j["srcs"][0].device))
 
     def arr(k):
         return hip_lib.ptr_array(cols[k]) if used[k] else None
@@ -263,20 +271,17 @@ def conv3x3_batch(jobs, cout, relu=False, shuffle=False, logical_w=None, outs=No
     common = (len(norm), hip_lib.ptr_array(src_ptrs), n_src, cps, hip_lib.ptr_array([j["wpk"].data_ptr() for j in norm]),
               arr("bias"), arr("res0"), arr("res1"), arr("mask"), arr("base"),
               hip_lib.ptr_array([o.data_ptr() for o in outs]), N, cout, H, W, P, 1 if relu else 0, 1 if shuffle else 0)
-    code = lib.larva_conv3x3_fwd_batch(*common, _stream())
-    if code == 801:  # hipErrorNotSupported: unaligned shape, one launch per job
+    if not _try_launch("larva_conv3x3_fwd_batch", *common):   # unaligned shape: one launch per job
         return [conv3x3(j["srcs"], j["wpk"], cout, bias=j.get("bias"), relu=relu, mask=j.get("mask"),
                         res0=j.get("res0"), res1=j.get("res1"), shuffle=shuffle, base=j.get("base"), out=o,
                         logical_w=logical_w)
                 for j, o in zip(norm, outs)]
-    hip_lib.check(code, "larva_conv3x3_fwd_batch")
     return outs
 
 
 def head_conv3_direct(x, w, bias=None, pitch=None):
     """nn.Conv2d(3, cout, 3, 1, 1) on the raw image: x [N][3][H][W], w [cout][3][3][3] -> [N][cout][H][P]
     (P = pitch or W; columns [W, P) zero)."""
-    lib = hip_lib.load()
     N, C, H, W = (int(v) for v in x.shape)
     cout = int(w.shape[0])
     if C != 3 or tuple(w.shape[1:]) != (3, 3, 3) or cout % 16:
@@ -285,8 +290,7 @@ def head_conv3_direct(x, w, bias=None, pitch=None):
     _chk(w, "w")
     P = W if pitch is None else int(pitch)
     out = torch.empty((N, cout, H, P), device=x.device, dtype=torch.float32)
-    hip_lib.check(lib.larva_head_conv3_direct(x.data_ptr(), w.data_ptr(), _opt(bias, "bias", (cout,)), out.data_ptr(),
-                                              N, cout, H, W, P, _stream()), "larva_head_conv3_direct")
+    _launch("larva_head_conv3_direct", x.data_ptr(), w.data_ptr(), _opt(bias, "bias", (cout,)), out.data_ptr(), N, cout, H, W, P)
     return out
 
 
@@ -296,10 +300,9 @@ def conv3x3_exit_l1_batch(jobs, cout, truth, gvalue, gscale, want_image):
     (gvalue * gscale) / numel; want_image[j]: also store exit j's image.  Returns (images (None where
     not wanted), partial-sum vectors, gradients [N][cout][H][W]) or None when the launch does not
     apply (unaligned operands, cout != 48): the caller then runs the conv and the L1 sweep separately."""
-    lib = hip_lib.load()
     if not 2 <= len(jobs) <= 4 or cout != 48:
         return None
-    norm = [dict(j, srcs=[j["srcs"]] if isinstance(j["srcs"], torch.Tensor) else list(j["srcs"])) for j in jobs]
+    norm = [dict(j, srcs=_src_list(j["srcs"])) for j in jobs]
     n_src = len(norm[0]["srcs"])
     N, cps, H, P = (int(v) for v in norm[0]["srcs"][0].shape)
     hr = (N, cout // 16, 4 * H, 4 * P)
@@ -307,7 +310,7 @@ def conv3x3_exit_l1_batch(jobs, cout, truth, gvalue, gscale, want_image):
     numel = float(truth.numel())
     import numpy as np
     gval = float((np.float32(gvalue) * np.float32(gscale)) * (np.float32(1.0) / np.float32(numel)))
-    npart = int(lib.larva_exit_l1_partials(N, H, P))
+    npart = int(hip_lib.load().larva_exit_l1_partials(N, H, P))
     src_ptrs, outs, grads, parts = [], [], [], []
     for j, want in zip(norm, want_image):
         if len(j["srcs"]) != n_src:
@@ -319,16 +322,14 @@ def conv3x3_exit_l1_batch(jobs, cout, truth, gvalue, gscale, want_image):
         outs.append(torch.empty(hr, device=truth.device, dtype=torch.float32) if want else None)
         grads.append(torch.empty((N, cout, H, P), device=truth.device, dtype=torch.float32))
         parts.append(torch.empty(npart, device=truth.device, dtype=torch.float32))
-    code = lib.larva_conv3x3_exit_l1_batch(
+    done = _try_launch(
+        "larva_conv3x3_exit_l1_batch",
         len(norm), hip_lib.ptr_array(src_ptrs), n_src, cps, hip_lib.ptr_array([j["wpk"].data_ptr() for j in norm]),
         hip_lib.ptr_array([j["bias"].data_ptr() for j in norm]), hip_lib.ptr_array([j["base"].data_ptr() for j in norm]),
         hip_lib.ptr_array([truth.data_ptr()] * len(norm)), hip_lib.ptr_array([None if o is None else o.data_ptr() for o in outs]),
         hip_lib.ptr_array([g.data_ptr() for g in grads]), hip_lib.ptr_array([p.data_ptr() for p in parts]),
-        gval, N, cout, H, P, P, _stream())
-    if code == 801:
-        return None
-    hip_lib.check(code, "larva_conv3x3_exit_l1_batch")
-    return outs, parts, grads
+        gval, N, cout, H, P, P)
+    return (outs, parts, grads) if done else None
 
 
 def wgrad_partial_floats(cout, cin, splits):
@@ -344,10 +345,24 @@ def wgrad_cu_share(cout, cin):
     return int(hip_lib.load().larva_wgrad_cu_share(int(cout), int(cin)))
 
 
+def _dw_slice(j, cout, cin):
+    """The dw [cout][cin_total][3][3] of a weight-gradient job and the channel slice it names, checked ->
+    (cin_off, cin_valid, cin_total)."""
+    dw = j["dw"]
+    _chk(dw, "dw")
+    if dw.dim() != 4 or int(dw.shape[0]) != cout or tuple(dw.shape[2:]) != (3, 3):
+        raise RuntimeError("larvanet_amd: dw must be [cout][cin_total][3][3]")
+    total = int(dw.shape[1])
+    off = int(j.get("cin_off", 0))
+    valid = int(j.get("cin_valid", cin))
+    if off < 0 or valid < 1 or valid > cin or off + valid > total:
+        raise RuntimeError("larvanet_amd: wgrad channel slice out of range")
+    return off, valid, total
+
+
 def conv3x3_wgrad(jobs, cout, cin, splits):
     """jobs: list (<= max_wgrad_jobs()) of dicts {dy, x, dw, db (or None), cin_off, cin_valid}; dw/db are
     overwritten.  All jobs share (N, cout, cin, H, W)."""
-    lib = hip_lib.load()
     if not 1 <= len(jobs) <= max_wgrad_jobs():
         raise RuntimeError("larvanet_amd: 1..%d wgrad jobs per call" % max_wgrad_jobs())
     N, _, H, W = (int(v) for v in jobs[0]["dy"].shape)
@@ -356,38 +371,25 @@ def conv3x3_wgrad(jobs, cout, cin, splits):
     for j in jobs:
         dys.append(_chk(j["dy"], "dy", (N, cout, H, W)))
         xs.append(_chk(j["x"], "x", (N, cin, H, W)))
-        dw = j["dw"]
-        _chk(dw, "dw")
-        if dw.dim() != 4 or int(dw.shape[0]) != cout or tuple(dw.shape[2:]) != (3, 3):
-            raise RuntimeError("larvanet_amd: dw must be [cout][cin_total][3][3]")
-        total = int(dw.shape[1])
-        off = int(j.get("cin_off", 0))
-        valid = int(j.get("cin_valid", cin))
-        if off < 0 or valid < 1 or valid > cin or off + valid > total:
-            raise RuntimeError("larvanet_amd: wgrad channel slice out of range")
-        part = j.get("partial")
-        if part is None:
-            part = torch.empty(nfl, device=dw.device, dtype=torch.float32)
-        _chk(part, "partial", (nfl,))
+        off, valid, total = _dw_slice(j, cout, cin)
+        part = _out(j.get("partial"), (nfl,), j["dw"].device, name="partial")
         keep.append(part)
         parts.append(part.data_ptr())
-        dws.append(dw.data_ptr())
+        dws.append(j["dw"].data_ptr())
         dbs.append(_opt(j.get("db"), "db", (cout,)))
         offs.append(off)
         valids.append(valid)
         totals.append(total)
-    code = lib.larva_conv3x3_wgrad(
-        hip_lib.ptr_array(dys), hip_lib.ptr_array(xs), hip_lib.ptr_array(parts), hip_lib.ptr_array(dws),
-        hip_lib.ptr_array(dbs), hip_lib.int_array(offs), hip_lib.int_array(valids), hip_lib.int_array(totals),
-        len(jobs), splits, N, cout, cin, H, W, _stream())
-    hip_lib.check(code, "larva_conv3x3_wgrad")
+    _launch("larva_conv3x3_wgrad",
+            hip_lib.ptr_array(dys), hip_lib.ptr_array(xs), hip_lib.ptr_array(parts), hip_lib.ptr_array(dws),
+            hip_lib.ptr_array(dbs), hip_lib.int_array(offs), hip_lib.int_array(valids), hip_lib.int_array(totals),
+            len(jobs), splits, N, cout, cin, H, W)
     return keep
 
 
 def conv3x3_wgrad_partial(jobs, cout, cin, splits):
     """Phase 1 only: jobs (<= 64 dicts {dy, x}) -> (partial tensors, splits actually used).
     Feed them to wgrad_reduce later (the partials must stay alive until then)."""
-    lib = hip_lib.load()
     if not 1 <= len(jobs) <= 64:
         raise RuntimeError("larvanet_amd: 1..64 wgrad jobs per call")
     N, _, H, W = (int(v) for v in jobs[0]["dy"].shape)
@@ -397,10 +399,9 @@ def conv3x3_wgrad_partial(jobs, cout, cin, splits):
     xs = [_chk(j["x"], "x", (N, cin, H, W)) for j in jobs]
     parts = [torch.empty(nfl, device=jobs[0]["dy"].device, dtype=torch.float32) for _ in jobs]
     used = ctypes.c_int(0)
-    code = lib.larva_conv3x3_wgrad_partial(
-        hip_lib.ptr_array(dys), hip_lib.ptr_array(xs), hip_lib.ptr_array([p.data_ptr() for p in parts]),
-        len(jobs), splits, N, cout, cin, H, W, ctypes.byref(used), _stream())
-    hip_lib.check(code, "larva_conv3x3_wgrad_partial")
+    _launch("larva_conv3x3_wgrad_partial",
+            hip_lib.ptr_array(dys), hip_lib.ptr_array(xs), hip_lib.ptr_array([p.data_ptr() for p in parts]),
+            len(jobs), splits, N, cout, cin, H, W, ctypes.byref(used))
     return parts, int(used.value)
 
 
@@ -424,21 +425,22 @@ def conv3x3_wgrad_partial_flat(jobs, cout, cin, nwg, head=None):
     parts = [torch.empty(nfl, device=dev, dtype=torch.float32) for _ in jobs]
     used = (ctypes.c_int * len(jobs))()
     if head is None:
-        code = lib.larva_conv3x3_wgrad_partial_flat(
+        done = _try_launch(
+            "larva_conv3x3_wgrad_partial_flat",
             hip_lib.ptr_array(dys), hip_lib.ptr_array(xs), hip_lib.ptr_array([p.data_ptr() for p in parts]),
-            len(jobs), int(nwg), N, cout, cin, H, W, used, _stream())
+            len(jobs), int(nwg), N, cout, cin, H, W, used)
     else:
         hcap = int(lib.larva_wgrad_flat_head_splits(len(jobs), int(nwg), tiles))
         hper = wgrad_partial_floats(48, 16, 1)
         hpart = torch.empty(hper * hcap, device=dev, dtype=torch.float32)
         hused = ctypes.c_int(0)
-        code = lib.larva_conv3x3_wgrad_partial_flat_head(
+        done = _try_launch(
+            "larva_conv3x3_wgrad_partial_flat_head",
             hip_lib.ptr_array(dys), hip_lib.ptr_array(xs), hip_lib.ptr_array([p.data_ptr() for p in parts]), len(jobs),
             _chk(head["dy"], "head dy", (N, 48, H, W)), _chk(head["x"], "head x", (N, 16, H, W)), hpart.data_ptr(),
-            int(nwg), N, H, W, used, ctypes.byref(hused), _stream())
-    if code == 801:
+            int(nwg), N, H, W, used, ctypes.byref(hused))
+    if not done:
         return None
-    hip_lib.check(code, "larva_conv3x3_wgrad_partial_flat")
     splits = [int(v) for v in used]
     per = wgrad_partial_floats(cout, cin, 1)
     out = [p[:per * s] for p, s in zip(parts, splits)]
@@ -465,24 +467,15 @@ def wgrad_reduce(jobs, cout=None, cin=None, loss=None):
     reduced in ONE launch; dw/db are overwritten.  cout/cin: the kernel shape of every job that does
     not carry its own.  loss = (terms, scales, divisor, out): the same launch also finishes
     loss_from_partials(terms, scales, divisor) into the 0-d tensor `out`."""
-    lib = hip_lib.load()
     if not 1 <= len(jobs) <= 64:
         raise RuntimeError("larvanet_amd: 1..64 reduce jobs per call")
     parts, dws, dbs, offs, valids, totals, splits, couts, cins = [], [], [], [], [], [], [], [], []
     for j in jobs:
         co, ci = int(j.get("cout", cout)), int(j.get("cin", cin))
-        dw = j["dw"]
-        _chk(dw, "dw")
-        if dw.dim() != 4 or int(dw.shape[0]) != co or tuple(dw.shape[2:]) != (3, 3):
-            raise RuntimeError("larvanet_amd: dw must be [cout][cin_total][3][3]")
-        total = int(dw.shape[1])
-        off = int(j.get("cin_off", 0))
-        valid = int(j.get("cin_valid", ci))
-        if off < 0 or valid < 1 or valid > ci or off + valid > total:
-            raise RuntimeError("larvanet_amd: wgrad channel slice out of range")
+        off, valid, total = _dw_slice(j, co, ci)
         sp = int(j["splits"])
         parts.append(_chk(j["partial"], "partial", (wgrad_partial_floats(co, ci, sp),)))
-        dws.append(dw.data_ptr())
+        dws.append(j["dw"].data_ptr())
         dbs.append(_opt(j.get("db"), "db", (co,)))
         offs.append(off)
         valids.append(valid)
@@ -494,15 +487,13 @@ def wgrad_reduce(jobs, cout=None, cin=None, loss=None):
               hip_lib.int_array(valids), hip_lib.int_array(totals), hip_lib.int_array(splits), hip_lib.int_array(couts),
               hip_lib.int_array(cins), len(jobs))
     if loss is None:
-        code = lib.larva_wgrad_reduce(*common, _stream())
+        _launch("larva_wgrad_reduce", *common)
     else:
         terms, scales, divisor, out = loss
         if not 1 <= len(terms) <= 8:
             raise RuntimeError("larvanet_amd: 1..8 loss terms")
         _chk(out, "loss", ())
-        ptrs, counts, sc = _loss_terms(terms, scales)
-        code = lib.larva_wgrad_reduce_with_loss(*common, ptrs, counts, sc, len(terms), float(divisor), out.data_ptr(), _stream())
-    hip_lib.check(code, "larva_wgrad_reduce")
+        _launch("larva_wgrad_reduce_with_loss", *common, *_loss_terms(terms, scales), len(terms), float(divisor), out.data_ptr())
 
 
 UPSAMPLE_MODES = {"bicubic": 0, "bilinear": 1}
@@ -511,14 +502,12 @@ UPSAMPLE_MODES = {"bicubic": 0, "bilinear": 1}
 def upsample4(x, mode="bicubic"):
     """F.interpolate(x, scale_factor=4, mode=mode, align_corners=False) (models/LarvaNet.py:283-285) for the two
     modes that call accepts for a 4-D input (nearest / area refuse align_corners, linear / trilinear the rank)."""
-    lib = hip_lib.load()
     if mode not in UPSAMPLE_MODES:
         raise RuntimeError("larvanet_amd: no x4 kernel for interpolate mode %r" % (mode,))
     N, C, H, W = (int(v) for v in x.shape)
     _chk(x, "x")
     out = torch.empty((N, C, 4 * H, 4 * W), device=x.device, dtype=torch.float32)
-    hip_lib.check(lib.larva_upsample4_fwd(x.data_ptr(), out.data_ptr(), N, C, H, W, UPSAMPLE_MODES[mode], _stream()),
-                  "larva_upsample4_fwd")
+    _launch("larva_upsample4_fwd", x.data_ptr(), out.data_ptr(), N, C, H, W, UPSAMPLE_MODES[mode])
     return out
 
 
@@ -526,63 +515,57 @@ def upsample(x, scale, mode="bicubic"):
     """F.interpolate(x, scale_factor=scale, mode=mode, align_corners=False) for scale 2, 3 or 4 (4 = upsample4)."""
     if int(scale) == 4:
         return upsample4(x, mode)
-    lib = hip_lib.load()
     if mode not in UPSAMPLE_MODES or int(scale) not in (2, 3):
         raise RuntimeError("larvanet_amd: no kernel for interpolate mode %r at x%s" % (mode, scale))
     s = int(scale)
     N, C, H, W = (int(v) for v in x.shape)
     _chk(x, "x")
     out = torch.empty((N, C, s * H, s * W), device=x.device, dtype=torch.float32)
-    hip_lib.check(lib.larva_upsample_fwd(x.data_ptr(), out.data_ptr(), N, C, H, W, s, UPSAMPLE_MODES[mode], _stream()),
-                  "larva_upsample_fwd")
+    _launch("larva_upsample_fwd", x.data_ptr(), out.data_ptr(), N, C, H, W, s, UPSAMPLE_MODES[mode])
     return out
 
 
 def pixel_shuffle_base(y, base, scale, channels=3, logical_w=None):
     """x2 / x3 exit image: PixelShuffle(scale)(y[:, :channels * scale**2]) (+ base) for the plain conv output y
     [N][cpad][H][P] (logical_w: the image is W <= P columns wide) -> [N][channels][scale H][scale W]."""
-    lib = hip_lib.load()
     s = int(scale)
     N, cpad, H, P = (int(v) for v in y.shape)
     W = P if logical_w is None else int(logical_w)
     _chk(y, "y")
     hr = (N, channels, s * H, s * W)
     out = torch.empty(hr, device=y.device, dtype=torch.float32)
-    hip_lib.check(lib.larva_pixel_shuffle_base(y.data_ptr(), _opt(base, "base", hr), out.data_ptr(), N, channels, cpad, H, W,
-                                               P, s, _stream()), "larva_pixel_shuffle_base")
+    _launch("larva_pixel_shuffle_base", y.data_ptr(), _opt(base, "base", hr), out.data_ptr(), N, channels, cpad, H, W, P, s)
     return out
 
 
-def _lr_of(hr, scale):
+def _lr_of(hr, scale, what="spatial dims must be"):
+    """(N, C, H, W) of the image `scale` times smaller than hr [N][C][scale H][scale W]."""
     N, C, HH, WW = (int(v) for v in hr.shape)
     if HH % scale or WW % scale:
-        raise RuntimeError("larvanet_amd: spatial dims must be divisible by %d" % scale)
+        raise RuntimeError("larvanet_amd: %s divisible by %d" % (what, scale))
     return N, C, HH // scale, WW // scale
 
 
 def pixel_unshuffle(g, scale, cpad):
     """PixelShuffle(scale) backward: [N][C][sH][sW] -> [N][cpad][H][W], channels [C s^2, cpad) zero."""
-    lib = hip_lib.load()
     s = int(scale)
     _chk(g, "g")
     N, C, H, W = _lr_of(g, s)
     out = torch.empty((N, cpad, H, W), device=g.device, dtype=torch.float32)
-    hip_lib.check(lib.larva_pixel_unshuffle(g.data_ptr(), out.data_ptr(), N, C, cpad, H, W, s, _stream()),
-                  "larva_pixel_unshuffle")
+    _launch("larva_pixel_unshuffle", g.data_ptr(), out.data_ptr(), N, C, cpad, H, W, s)
     return out
 
 
 def l1_bwd_unshuffle(a, b, gout, scale, cpad, gscale=1.0):
     """Gradient of mean|a - b| * gscale w.r.t. a at scale 2 / 3, written as [N][cpad][H][W] (padding channels zero)."""
-    lib = hip_lib.load()
     s = int(scale)
     _chk(a, "a")
     _chk(b, "b", a.shape)
     _chk(gout, "gout", ())
     N, C, H, W = _lr_of(a, s)
     out = torch.empty((N, cpad, H, W), device=a.device, dtype=torch.float32)
-    hip_lib.check(lib.larva_l1_bwd_unshuffle(a.data_ptr(), b.data_ptr(), gout.data_ptr(), float(gscale), out.data_ptr(),
-                                             N, C, cpad, H, W, s, _stream()), "larva_l1_bwd_unshuffle")
+    _launch("larva_l1_bwd_unshuffle", a.data_ptr(), b.data_ptr(), gout.data_ptr(), float(gscale), out.data_ptr(),
+            N, C, cpad, H, W, s)
     return out
 
 
@@ -590,109 +573,96 @@ def shuffle_l1_partial_grad(y, base, truth, gvalue, gscale, scale, want_image=Tr
     """One x2 / x3 training exit after its plain conv y [N][cpad][H][W]: -> (partials, 1 / numel, grad [N][cpad][H][W],
     image = PixelShuffle(scale)(y) + base or None), the L1 partial sums and the gradient sign(image - truth) * gvalue *
     gscale / numel from one pass."""
-    lib = hip_lib.load()
     s = int(scale)
     _chk(truth, "truth")
     N, C, H, W = _lr_of(truth, s)
     cpad = int(y.shape[1])
     _chk(y, "y", (N, cpad, H, W))
     _chk(base, "base", truth.shape)
-    part = torch.empty(int(lib.larva_l1_workspace_floats()), device=y.device, dtype=torch.float32)
+    part = _l1_partials(y.device)
     grad = torch.empty((N, cpad, H, W), device=y.device, dtype=torch.float32)
     out = torch.empty(truth.shape, device=y.device, dtype=torch.float32) if want_image else None
     blocks = ctypes.c_int(0)
-    hip_lib.check(lib.larva_shuffle_l1_partial_grad(y.data_ptr(), base.data_ptr(), truth.data_ptr(), float(gvalue),
-                                                    float(gscale), part.data_ptr(), ctypes.byref(blocks), grad.data_ptr(),
-                                                    None if out is None else out.data_ptr(), N, C, cpad, H, W, s, _stream()),
-                  "larva_shuffle_l1_partial_grad")
+    _launch("larva_shuffle_l1_partial_grad", y.data_ptr(), base.data_ptr(), truth.data_ptr(), float(gvalue), float(gscale),
+            part.data_ptr(), ctypes.byref(blocks), grad.data_ptr(), None if out is None else out.data_ptr(), N, C, cpad, H, W, s)
     return part[:int(blocks.value)], 1.0 / float(truth.numel()), grad, out
 
 
 def bicubic4(x):
-    lib = hip_lib.load()
     N, C, H, W = (int(v) for v in x.shape)
     _chk(x, "x")
     out = torch.empty((N, C, 4 * H, 4 * W), device=x.device, dtype=torch.float32)
-    hip_lib.check(lib.larva_bicubic4_fwd(x.data_ptr(), out.data_ptr(), N, C, H, W, _stream()), "larva_bicubic4_fwd")
+    _launch("larva_bicubic4_fwd", x.data_ptr(), out.data_ptr(), N, C, H, W)
     return out
 
 
 _L1_WORKSPACES = {}
 
 
+def _l1_partials(device):
+    """A new buffer for the block partial sums of one L1 launch."""
+    return torch.empty(int(hip_lib.load().larva_l1_workspace_floats()), device=device, dtype=torch.float32)
+
+
 def _l1_workspace(device):
     """Block partial sums of l1_fwd, one buffer per (device, stream)."""
-    lib = hip_lib.load()
     key = (str(device), torch.cuda.current_stream().cuda_stream)
     ws = _L1_WORKSPACES.get(key)
     if ws is None:
-        ws = torch.empty(int(lib.larva_l1_workspace_floats()), device=device, dtype=torch.float32)
-        _L1_WORKSPACES[key] = ws
+        ws = _L1_WORKSPACES[key] = _l1_partials(device)
     return ws
 
 
 def l1_fwd(a, b):
     """mean |a - b| as a 0-d device tensor (one launch)."""
-    lib = hip_lib.load()
     _chk(a, "a")
     _chk(b, "b", a.shape)
     ws = _l1_workspace(a.device)
     loss = torch.empty((), device=a.device, dtype=torch.float32)
-    hip_lib.check(lib.larva_l1_fwd(a.data_ptr(), b.data_ptr(), a.numel(), ws.data_ptr(), loss.data_ptr(), _stream()),
-                  "larva_l1_fwd")
+    _launch("larva_l1_fwd", a.data_ptr(), b.data_ptr(), a.numel(), ws.data_ptr(), loss.data_ptr())
     return loss
 
 
 def l1_partial(a, b):
     """Block partial sums of sum|a - b| -> (partials [blocks], 1 / numel): an L1 term that
     loss_from_partials finishes together with the other exits' terms."""
-    lib = hip_lib.load()
     _chk(a, "a")
     _chk(b, "b", a.shape)
-    part = torch.empty(int(lib.larva_l1_workspace_floats()), device=a.device, dtype=torch.float32)
+    part = _l1_partials(a.device)
     blocks = ctypes.c_int(0)
-    hip_lib.check(lib.larva_l1_partial(a.data_ptr(), b.data_ptr(), a.numel(), part.data_ptr(), ctypes.byref(blocks),
-                                       _stream()), "larva_l1_partial")
+    _launch("larva_l1_partial", a.data_ptr(), b.data_ptr(), a.numel(), part.data_ptr(), ctypes.byref(blocks))
     return part[:int(blocks.value)], 1.0 / float(a.numel())
 
 
 def l1_partial_grad(a, b, gvalue, gscale):
     """l1_partial + l1_bwd_unshuffle4 in one pass, for an upstream gradient known on the host:
     -> (partials, 1 / numel, grad [N][16C][H][W])."""
-    lib = hip_lib.load()
     _chk(a, "a")
     _chk(b, "b", a.shape)
-    N, C, HH, WW = (int(v) for v in a.shape)
-    if HH % 4 or WW % 4:
-        raise RuntimeError("larvanet_amd: spatial dims must be divisible by 4")
-    part = torch.empty(int(lib.larva_l1_workspace_floats()), device=a.device, dtype=torch.float32)
-    grad = torch.empty((N, 16 * C, HH // 4, WW // 4), device=a.device, dtype=torch.float32)
+    N, C, H, W = _lr_of(a, 4)
+    part = _l1_partials(a.device)
+    grad = torch.empty((N, 16 * C, H, W), device=a.device, dtype=torch.float32)
     blocks = ctypes.c_int(0)
-    hip_lib.check(lib.larva_l1_partial_grad(a.data_ptr(), b.data_ptr(), float(gvalue), float(gscale), part.data_ptr(),
-                                            ctypes.byref(blocks), grad.data_ptr(), N, C, HH // 4, WW // 4, _stream()),
-                  "larva_l1_partial_grad")
+    _launch("larva_l1_partial_grad", a.data_ptr(), b.data_ptr(), float(gvalue), float(gscale), part.data_ptr(),
+            ctypes.byref(blocks), grad.data_ptr(), N, C, H, W)
     return part[:int(blocks.value)], 1.0 / float(a.numel()), grad
 
 
 def l1_partial_grad_batch(outs, truth, gvalue, gscale):
     """l1_partial_grad for several exit images against one truth in one launch ->
     ([partials], 1 / numel, [grads])."""
-    lib = hip_lib.load()
     if not 1 <= len(outs) <= 8:
         raise RuntimeError("larvanet_amd: 1..8 images per batched L1 sweep")
     _chk(truth, "truth")
-    N, C, HH, WW = (int(v) for v in truth.shape)
-    if HH % 4 or WW % 4:
-        raise RuntimeError("larvanet_amd: spatial dims must be divisible by 4")
+    N, C, H, W = _lr_of(truth, 4)
     ptrs = [_chk(o, "out", truth.shape) for o in outs]
-    nws = int(lib.larva_l1_workspace_floats())
-    parts = [torch.empty(nws, device=truth.device, dtype=torch.float32) for _ in outs]
-    grads = [torch.empty((N, 16 * C, HH // 4, WW // 4), device=truth.device, dtype=torch.float32) for _ in outs]
+    parts = [_l1_partials(truth.device) for _ in outs]
+    grads = [torch.empty((N, 16 * C, H, W), device=truth.device, dtype=torch.float32) for _ in outs]
     blocks = ctypes.c_int(0)
-    hip_lib.check(lib.larva_l1_partial_grad_batch(
-        hip_lib.ptr_array(ptrs), truth.data_ptr(), len(outs), float(gvalue), float(gscale),
-        hip_lib.ptr_array([p.data_ptr() for p in parts]), ctypes.byref(blocks),
-        hip_lib.ptr_array([g.data_ptr() for g in grads]), N, C, HH // 4, WW // 4, _stream()), "larva_l1_partial_grad_batch")
+    _launch("larva_l1_partial_grad_batch",
+            hip_lib.ptr_array(ptrs), truth.data_ptr(), len(outs), float(gvalue), float(gscale),
+            hip_lib.ptr_array([p.data_ptr() for p in parts]), ctypes.byref(blocks),
+            hip_lib.ptr_array([g.data_ptr() for g in grads]), N, C, H, W)
     nb = int(blocks.value)
     return [p[:nb] for p in parts], 1.0 / float(truth.numel()), grads
 
@@ -704,7 +674,7 @@ class HostCell:
 
     def __init__(self):
         p = ctypes.c_void_p()
-        hip_lib.check(hip_lib.load().larva_host_cell_alloc(ctypes.byref(p)), "larva_host_cell_alloc")
+        _launch("larva_host_cell_alloc", ctypes.byref(p), stream=False)
         self.ptr = int(p.value)
         self._cell = ctypes.c_uint64.from_address(self.ptr)
         self.expected = 0
@@ -742,114 +712,90 @@ class HostCell:
 def loss_from_partials(terms, scales, divisor, host_cell=None):
     """( sum_i scales[i] * terms[i].sum() ) / divisor as a 0-d tensor, one launch, fixed order; host_cell
     (HostCell) receives the value too."""
-    lib = hip_lib.load()
     if not 1 <= len(terms) <= 8:
         raise RuntimeError("larvanet_amd: 1..8 loss terms")
     out = torch.empty((), device=terms[0].device, dtype=torch.float32)
-    hip_lib.check(lib.larva_loss_from_partials_to_host_seq(
-        *_loss_terms(terms, scales), len(terms), float(divisor), out.data_ptr(),
-        host_cell.ptr if host_cell is not None else None,
-        host_cell.dev_seq.data_ptr() if host_cell is not None and host_cell.dev_seq is not None else None, _stream()),
-        "larva_loss_from_partials_to_host")
+    _launch("larva_loss_from_partials_to_host_seq",
+            *_loss_terms(terms, scales), len(terms), float(divisor), out.data_ptr(),
+            host_cell.ptr if host_cell is not None else None,
+            host_cell.dev_seq.data_ptr() if host_cell is not None and host_cell.dev_seq is not None else None)
     return out
 
 
 def l1_bwd_unshuffle4(a, b, gout, gscale=1.0):
     """Gradient of mean|a - b| * gscale w.r.t. a, written as [N][16C][H][W] (pixel-unshuffled)."""
-    lib = hip_lib.load()
     _chk(a, "a")
     _chk(b, "b", a.shape)
     _chk(gout, "gout", ())
-    N, C, HH, WW = (int(v) for v in a.shape)
-    if HH % 4 or WW % 4:
-        raise RuntimeError("larvanet_amd: spatial dims must be divisible by 4")
-    out = torch.empty((N, 16 * C, HH // 4, WW // 4), device=a.device, dtype=torch.float32)
-    hip_lib.check(lib.larva_l1_bwd_unshuffle4(a.data_ptr(), b.data_ptr(), gout.data_ptr(), float(gscale),
-                                              out.data_ptr(), N, C, HH // 4, WW // 4, _stream()),
-                  "larva_l1_bwd_unshuffle4")
+    N, C, H, W = _lr_of(a, 4)
+    out = torch.empty((N, 16 * C, H, W), device=a.device, dtype=torch.float32)
+    _launch("larva_l1_bwd_unshuffle4", a.data_ptr(), b.data_ptr(), gout.data_ptr(), float(gscale), out.data_ptr(), N, C, H, W)
     return out
 
 
 def sum_scalars(terms, divisor):
-    lib = hip_lib.load()
     ptrs = [_chk(t, "term", ()) for t in terms]
     out = torch.empty((), device=terms[0].device, dtype=torch.float32)
-    hip_lib.check(lib.larva_sum_scalars(hip_lib.ptr_array(ptrs), len(ptrs), float(divisor), out.data_ptr(), _stream()),
-                  "larva_sum_scalars")
+    _launch("larva_sum_scalars", hip_lib.ptr_array(ptrs), len(ptrs), float(divisor), out.data_ptr())
     return out
 
 
 def l1_bwd(a, b, gout):
-    lib = hip_lib.load()
     _chk(a, "a")
     _chk(b, "b", a.shape)
     _chk(gout, "gout", ())
     ga = torch.empty_like(a)
-    hip_lib.check(lib.larva_l1_bwd(a.data_ptr(), b.data_ptr(), gout.data_ptr(), a.numel(), ga.data_ptr(), _stream()),
-                  "larva_l1_bwd")
+    _launch("larva_l1_bwd", a.data_ptr(), b.data_ptr(), gout.data_ptr(), a.numel(), ga.data_ptr())
     return ga
 
 
 def pixel_unshuffle4(g):
-    lib = hip_lib.load()
     _chk(g, "g")
-    N, C, HH, WW = (int(v) for v in g.shape)
-    if HH % 4 or WW % 4:
-        raise RuntimeError("larvanet_amd: pixel_unshuffle4 needs spatial dims divisible by 4")
-    H, W = HH // 4, WW // 4
+    N, C, H, W = _lr_of(g, 4, "pixel_unshuffle4 needs spatial dims")
     out = torch.empty((N, 16 * C, H, W), device=g.device, dtype=torch.float32)
-    hip_lib.check(lib.larva_pixel_unshuffle4(g.data_ptr(), out.data_ptr(), N, C, H, W, _stream()),
-                  "larva_pixel_unshuffle4")
+    _launch("larva_pixel_unshuffle4", g.data_ptr(), out.data_ptr(), N, C, H, W)
     return out
 
 
 def adamw_step(p, g, m, v, step_lr, beta1, beta2, eps, weight_decay, grad_scale=1.0):
-    lib = hip_lib.load()
     n = p.numel()
     for t, name in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
         _chk(t, name, (n,))
     _chk(step_lr, "step_lr", (2,))
-    hip_lib.check(lib.larva_adamw_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), step_lr.data_ptr(),
-                                       beta1, beta2, eps, weight_decay, grad_scale, n, _stream()),
-                  "larva_adamw_step")
+    _launch("larva_adamw_step", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), step_lr.data_ptr(),
+            beta1, beta2, eps, weight_decay, grad_scale, n)
 
 
 def gather_patches(data, offsets, hw, draws, batch, patch, mult, out=None):
     """Augmented float patches [batch][3][patch][patch] from a uint8 dataset resident on the device
     (into `out` when given: e.g. the input buffer a captured training step reads)."""
-    lib = hip_lib.load()
     for t, name, dt in ((data, "data", torch.uint8), (offsets, "offsets", torch.int64), (hw, "hw", torch.int32),
                         (draws, "draws", torch.int32)):
         if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
             raise RuntimeError("larvanet_amd: %s must be a contiguous %s tensor on the HIP device" % (name, dt))
     if tuple(draws.shape) != (batch, 5):
         raise RuntimeError("larvanet_amd: draws must be [batch][5]")
-    if out is None:
-        out = torch.empty((batch, 3, patch, patch), device=data.device, dtype=torch.float32)
-    _chk(out, "out", (batch, 3, patch, patch))
-    hip_lib.check(lib.larva_gather_patches(data.data_ptr(), offsets.data_ptr(), hw.data_ptr(), draws.data_ptr(),
-                                           out.data_ptr(), batch, patch, mult, _stream()), "larva_gather_patches")
+    out = _out(out, (batch, 3, patch, patch), data.device)
+    _launch("larva_gather_patches", data.data_ptr(), offsets.data_ptr(), hw.data_ptr(), draws.data_ptr(),
+            out.data_ptr(), batch, patch, mult)
     return out
 
 
 def adamw_step_host(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay, grad_scale=1.0, copy=None):
     """One AdamW step over flat buffers, step count and learning rate given by the host.  copy = (src, dst):
     the launch also copies the 0-d tensor src into dst (the step's loss out of a captured graph's buffer)."""
-    lib = hip_lib.load()
     n = p.numel()
     for t, name in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
         _chk(t, name, (n,))
-    if copy is not None:
+    args = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), int(step), float(lr), beta1, beta2, eps, weight_decay,
+            grad_scale, n)
+    if copy is None:
+        _launch("larva_adamw_step_host", *args)
+    else:
         src, dst = copy
         _chk(src, "copy source", ())
         _chk(dst, "copy destination", ())
-        hip_lib.check(lib.larva_adamw_step_host_copy(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), int(step),
-                                                     float(lr), beta1, beta2, eps, weight_decay, grad_scale, n,
-                                                     src.data_ptr(), dst.data_ptr(), _stream()), "larva_adamw_step_host_copy")
-        return
-    hip_lib.check(lib.larva_adamw_step_host(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), int(step),
-                                            float(lr), beta1, beta2, eps, weight_decay, grad_scale, n, _stream()),
-                  "larva_adamw_step_host")
+        _launch("larva_adamw_step_host_copy", *args, src.data_ptr(), dst.data_ptr())
 
 
 def psnr_u8(out_chw, truth_u8):
@@ -857,7 +803,6 @@ def psnr_u8(out_chw, truth_u8):
     truth_u8 uint8 [C][TH][TW] (device), truth cropped top-left to the output size.  Returns a float
     (one 8-byte read-back instead of the whole HR image)."""
     import math
-    lib = hip_lib.load()
     _chk(out_chw, "out")
     if not truth_u8.is_cuda or truth_u8.dtype != torch.uint8 or not truth_u8.is_contiguous():
         raise RuntimeError("larvanet_amd: truth must be a contiguous uint8 tensor on the HIP device")
@@ -866,8 +811,7 @@ def psnr_u8(out_chw, truth_u8):
     if TC != C or TH < H or TW < W:
         raise RuntimeError("larvanet_amd: truth image smaller than the output")
     acc = torch.zeros(1, device=out_chw.device, dtype=torch.int64)
-    hip_lib.check(lib.larva_sqerr_u8(out_chw.data_ptr(), truth_u8.data_ptr(), C, H, W, TH, TW, acc.data_ptr(),
-                                     _stream()), "larva_sqerr_u8")
+    _launch("larva_sqerr_u8", out_chw.data_ptr(), truth_u8.data_ptr(), C, H, W, TH, TW, acc.data_ptr())
     sq = int(acc.item())
     mse = sq / float(C * H * W)
     return float("inf") if mse == 0 else 10.0 * math.log10(255.0 ** 2 / mse)
@@ -901,7 +845,6 @@ def f16_packed_weight_halves(cout, cin):
 
 def f16_pack_weights(w, out=None):
     """[48][48 m][3][3] fp32 weight -> its fp16 A-operand image (flat float16 tensor, include/larva_hip.h)."""
-    lib = hip_lib.load()
     _chk(w, "w")
     if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
         raise RuntimeError("larvanet_amd: only [cout][cin][3][3] weights are supported")
@@ -913,33 +856,27 @@ def f16_pack_weights(w, out=None):
         out = torch.empty(n, device=w.device, dtype=torch.float16)
     if out.dtype != torch.float16 or out.numel() != n or not out.is_contiguous():
         raise RuntimeError("larvanet_amd: fp16 weight image must be %d contiguous halves" % n)
-    hip_lib.check(lib.larva_f16_pack_weights(w.data_ptr(), out.data_ptr(), cout, cin, _stream()), "larva_f16_pack_weights")
+    _launch("larva_f16_pack_weights", w.data_ptr(), out.data_ptr(), cout, cin)
     return out
 
 
 def f16_head(x, w, bias, flag, out=None):
     """x fp32 [N][3][H][W] -> fp16 [N][H][W][48] = conv(x, w) + bias (fp32 operands, one rounding to fp16)."""
-    lib = hip_lib.load()
     N, C, H, W = (int(v) for v in x.shape)
     _chk(x, "x")
     _chk(w, "w", (F16_CHANNELS, 3, 3, 3))
     _chk(bias, "bias", (F16_CHANNELS,))
     if C != 3:
         raise RuntimeError("larvanet_amd: the fp16 head takes 3-channel images")
-    if out is None:
-        out = torch.empty((N, H, W, F16_CHANNELS), device=x.device, dtype=torch.float16)
-    _chk16(out, "out", (N, H, W, F16_CHANNELS))
-    hip_lib.check(lib.larva_f16_head(x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), _chk_flag(flag), N, H, W,
-                                     _stream()), "larva_f16_head")
+    out = _out(out, (N, H, W, F16_CHANNELS), x.device, torch.float16, F16_CHANNELS)
+    _launch("larva_f16_head", x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), _chk_flag(flag), N, H, W)
     return out
 
 
 def f16_conv3x3(srcs, wpk, bias, flag, relu=False, res0=None, res1=None, out=None):
     """48 -> 48 conv over the fp16 tensors `srcs` (consecutive 48-channel K chunks), + bias, then ReLU or + res0
     (+ res1), rounded once to fp16 -> [N][H][W][48]."""
-    lib = hip_lib.load()
-    if isinstance(srcs, torch.Tensor):
-        srcs = [srcs]
+    srcs = _src_list(srcs)
     if not 1 <= len(srcs) <= F16_MAX_SOURCES:
         raise RuntimeError("larvanet_amd: the fp16 conv takes 1 to %d inputs" % F16_MAX_SOURCES)
     shape = tuple(srcs[0].shape)
@@ -953,18 +890,14 @@ def f16_conv3x3(srcs, wpk, bias, flag, relu=False, res0=None, res1=None, out=Non
         raise RuntimeError("larvanet_amd: res1 needs res0")
     r0 = None if res0 is None else _chk16(res0, "res0", shape)
     r1 = None if res1 is None else _chk16(res1, "res1", shape)
-    if out is None:
-        out = torch.empty(shape, device=srcs[0].device, dtype=torch.float16)
-    _chk16(out, "out", shape)
-    hip_lib.check(lib.larva_f16_conv3x3(hip_lib.ptr_array(ptrs), len(ptrs), wpk.data_ptr(), bias.data_ptr(), r0, r1,
-                                        int(bool(relu)), out.data_ptr(), _chk_flag(flag), N, H, W, _stream()),
-                  "larva_f16_conv3x3")
+    out = _out(out, shape, srcs[0].device, torch.float16, F16_CHANNELS)
+    _launch("larva_f16_conv3x3", hip_lib.ptr_array(ptrs), len(ptrs), wpk.data_ptr(), bias.data_ptr(), r0, r1,
+            int(bool(relu)), out.data_ptr(), _chk_flag(flag), N, H, W)
     return out
 
 
 def f16_conv3x3_shuffle_base(src, wpk, bias, base):
     """Leg end: fp32 [N][3][4H][4W] = PixelShuffle(4)(conv(src) + bias) + base, src fp16 [N][H][W][48]."""
-    lib = hip_lib.load()
     _chk16(src, "src")
     N, H, W = (int(v) for v in src.shape[:3])
     _chk_wpk16(wpk, 1, "48 -> 48")
@@ -972,26 +905,22 @@ def f16_conv3x3_shuffle_base(src, wpk, bias, base):
     hr = (N, 3, 4 * H, 4 * W)
     _chk(base, "base", hr)
     out = torch.empty(hr, device=src.device, dtype=torch.float32)
-    hip_lib.check(lib.larva_f16_conv3x3_shuffle_base(src.data_ptr(), wpk.data_ptr(), bias.data_ptr(), base.data_ptr(),
-                                                     out.data_ptr(), N, H, W, _stream()), "larva_f16_conv3x3_shuffle_base")
+    _launch("larva_f16_conv3x3_shuffle_base", src.data_ptr(), wpk.data_ptr(), bias.data_ptr(), base.data_ptr(),
+            out.data_ptr(), N, H, W)
     return out
 
 
 def f16_conv3x3_shuffle_base_u8(src, wpk, bias, base, flag, out=None):
     """The leg end as a uint8 image: uint8 [N][4H][4W][3] = f32_chw_to_u8_hwc(f16_conv3x3_shuffle_base(...)), bit for
     bit, in one launch (the fp32 HR image is never stored).  A non-finite value sets `flag`."""
-    lib = hip_lib.load()
     _chk16(src, "src")
     N, H, W = (int(v) for v in src.shape[:3])
     _chk_wpk16(wpk, 1, "48 -> 48")
     _chk(bias, "bias", (F16_CHANNELS,))
     _chk(base, "base", (N, 3, 4 * H, 4 * W))
-    if out is None:
-        out = torch.empty((N, 4 * H, 4 * W, 3), device=src.device, dtype=torch.uint8)
-    _chk_u8(out, "out", (N, 4 * H, 4 * W, 3))
-    hip_lib.check(lib.larva_f16_conv3x3_shuffle_base_u8(src.data_ptr(), wpk.data_ptr(), bias.data_ptr(), base.data_ptr(),
-                                                        out.data_ptr(), _chk_flag(flag), N, H, W, _stream()),
-                  "larva_f16_conv3x3_shuffle_base_u8")
+    out = _out(out, (N, 4 * H, 4 * W, 3), src.device, torch.uint8, 3)
+    _launch("larva_f16_conv3x3_shuffle_base_u8", src.data_ptr(), wpk.data_ptr(), bias.data_ptr(), base.data_ptr(),
+            out.data_ptr(), _chk_flag(flag), N, H, W)
     return out
 
 
@@ -1014,15 +943,10 @@ def _chk_f16_jobs(srcs, wpks, biases):
 def f16_conv3x3_jobs(srcs, wpks, biases, flag, relu=False, out=None):
     """len(srcs) (1..8) independent 48 -> 48 convs of one shape in ONE launch: job j = f16_conv3x3(srcs[j], wpks[j],
     biases[j], relu=relu), bit for bit -> fp16 [njobs][N][H][W][48] (one tensor; out[j] is job j's)."""
-    lib = hip_lib.load()
     (N, H, W), arrays = _chk_f16_jobs(srcs, wpks, biases)
-    shape = (len(srcs), N, H, W, F16_CHANNELS)
-    if out is None:
-        out = torch.empty(shape, device=srcs[0].device, dtype=torch.float16)
-    _chk_tensor(out, "out", shape, torch.float16)
+    out = _out(out, (len(srcs), N, H, W, F16_CHANNELS), srcs[0].device, torch.float16)
     outs = hip_lib.ptr_array([out[j].data_ptr() for j in range(len(srcs))])
-    hip_lib.check(lib.larva_f16_conv3x3_jobs(len(srcs), *arrays, int(bool(relu)), outs, _chk_flag(flag), N, H, W, _stream()),
-                  "larva_f16_conv3x3_jobs")
+    _launch("larva_f16_conv3x3_jobs", len(srcs), *arrays, int(bool(relu)), outs, _chk_flag(flag), N, H, W)
     return out
 
 
@@ -1030,19 +954,15 @@ def f16_conv3x3_shuffle_base_jobs(srcs, wpks, biases, base, flag=None, u8=False,
     """The leg end of every job against one shared base, in ONE launch: job j = f16_conv3x3_shuffle_base(srcs[j], wpks[j],
     biases[j], base) -> fp32 [njobs][N][3][4H][4W], or with u8 f16_conv3x3_shuffle_base_u8(...) -> uint8
     [njobs][N][4H][4W][3] (needs flag), bit for bit."""
-    lib = hip_lib.load()
     (N, H, W), arrays = _chk_f16_jobs(srcs, wpks, biases)
     _chk(base, "base", (N, 3, 4 * H, 4 * W))
     M = len(srcs)
     shape, dtype = ((M, N, 4 * H, 4 * W, 3), torch.uint8) if u8 else ((M, N, 3, 4 * H, 4 * W), torch.float32)
-    if out is None:
-        out = torch.empty(shape, device=srcs[0].device, dtype=dtype)
-    _chk_tensor(out, "out", shape, dtype)
+    out = _out(out, shape, srcs[0].device, dtype)
     outs = hip_lib.ptr_array([out[j].data_ptr() for j in range(M)])
     fl = _chk_flag(flag) if (u8 or flag is not None) else None
-    hip_lib.check(lib.larva_f16_conv3x3_shuffle_base_jobs(M, *arrays, base.data_ptr(), None if u8 else outs,
-                                                          outs if u8 else None, fl, N, H, W, _stream()),
-                  "larva_f16_conv3x3_shuffle_base_jobs")
+    _launch("larva_f16_conv3x3_shuffle_base_jobs", M, *arrays, base.data_ptr(), None if u8 else outs, outs if u8 else None,
+            fl, N, H, W)
     return out
 
 
@@ -1054,28 +974,22 @@ def _chk_u8(t, name, shape=None):
 
 def u8_hwc_to_f32_chw(x, out=None):
     """uint8 [N][H][W][3] (decoded images) -> float32 [N][3][H][W], exact."""
-    lib = hip_lib.load()
     _chk_u8(x, "x")
     N, H, W = (int(v) for v in x.shape[:3])
-    if out is None:
-        out = torch.empty((N, 3, H, W), device=x.device, dtype=torch.float32)
-    _chk(out, "out", (N, 3, H, W))
-    hip_lib.check(lib.larva_u8_hwc_to_f32_chw(x.data_ptr(), out.data_ptr(), N, H, W, _stream()), "larva_u8_hwc_to_f32_chw")
+    out = _out(out, (N, 3, H, W), x.device)
+    _launch("larva_u8_hwc_to_f32_chw", x.data_ptr(), out.data_ptr(), N, H, W)
     return out
 
 
 def f32_chw_to_u8_hwc(x, out=None):
     """float32 [N][3][H][W] -> uint8 [N][H][W][3] = clip(round half to even(x), 0, 255): metrics.image_to_uint8 on the
     device, transposed for an image writer."""
-    lib = hip_lib.load()
     _chk(x, "x")
     if x.dim() != 4 or int(x.shape[1]) != 3:
         raise RuntimeError("larvanet_amd: x must be [N][3][H][W], got %s" % (tuple(x.shape),))
     N, _, H, W = (int(v) for v in x.shape)
-    if out is None:
-        out = torch.empty((N, H, W, 3), device=x.device, dtype=torch.uint8)
-    _chk_u8(out, "out", (N, H, W, 3))
-    hip_lib.check(lib.larva_f32_chw_to_u8_hwc(x.data_ptr(), out.data_ptr(), N, H, W, _stream()), "larva_f32_chw_to_u8_hwc")
+    out = _out(out, (N, H, W, 3), x.device, torch.uint8, 3)
+    _launch("larva_f32_chw_to_u8_hwc", x.data_ptr(), out.data_ptr(), N, H, W)
     return out
 
 
@@ -1084,26 +998,22 @@ def dihedral_inputs(x, out=None):
     """The eight dihedral images (image_utils.dihedral) of x, uint8 [N][H][W][3] or float32 [N][3][H][W], as batch slots,
     exact, in one launch -> (A float32 [4N][3][H][W], B float32 [4N][3][W][H]): image n under t is A[4 n + t] for t < 4
     and B[4 n + t - 4] for t >= 4.  out = (A, B) to fill the caller's buffers."""
-    lib = hip_lib.load()
     if isinstance(x, torch.Tensor) and x.dtype == torch.uint8:
         _chk_u8(x, "x")
         N, H, W = (int(v) for v in x.shape[:3])
-        fn, name = lib.larva_dihedral_inputs_u8, "larva_dihedral_inputs_u8"
+        name = "larva_dihedral_inputs_u8"
     else:
         _chk(x, "x")
         if x.dim() != 4 or int(x.shape[1]) != 3:
             raise RuntimeError("larvanet_amd: x must be uint8 [N][H][W][3] or float32 [N][3][H][W], got %s" % (tuple(x.shape),))
         N, _, H, W = (int(v) for v in x.shape)
-        fn, name = lib.larva_dihedral_inputs_f32, "larva_dihedral_inputs_f32"
+        name = "larva_dihedral_inputs_f32"
     if min(N, H, W) < 1:
         raise RuntimeError("larvanet_amd: x must not be empty, got %s" % (tuple(x.shape),))
-    if out is None:
-        out = (torch.empty((4 * N, 3, H, W), device=x.device, dtype=torch.float32),
-               torch.empty((4 * N, 3, W, H), device=x.device, dtype=torch.float32))
-    a, b = out
-    _chk(a, "A", (4 * N, 3, H, W))
-    _chk(b, "B", (4 * N, 3, W, H))
-    hip_lib.check(fn(x.data_ptr(), a.data_ptr(), b.data_ptr(), N, H, W, _stream()), name)
+    a, b = (None, None) if out is None else out
+    a = _out(a, (4 * N, 3, H, W), x.device, name="A")
+    b = _out(b, (4 * N, 3, W, H), x.device, name="B")
+    _launch(name, x.data_ptr(), a.data_ptr(), b.data_ptr(), N, H, W)
     return a, b
 
 
@@ -1111,7 +1021,6 @@ def dihedral_mean(a, b, u8=False, out=None):
     """The self-ensemble's merge in one launch: a float32 [4N][3][H][W] and b float32 [4N][3][W][H] (the forward's outputs
     for dihedral_inputs' A and B) -> the fixed-order fp32 mean of the eight images mapped back (image_utils.dihedral_inv),
     float32 [N][3][H][W], or with u8 its uint8 [N][H][W][3] form (f32_chw_to_u8_hwc of the former, bit for bit)."""
-    lib = hip_lib.load()
     _chk(a, "A")
     if a.dim() != 4 or int(a.shape[1]) != 3 or int(a.shape[0]) % 4 or min(a.shape) < 1:
         raise RuntimeError("larvanet_amd: A must be [4N][3][H][W], got %s" % (tuple(a.shape),))
@@ -1121,16 +1030,12 @@ def dihedral_mean(a, b, u8=False, out=None):
         raise RuntimeError("larvanet_amd: A and B must be on one device")
     N = n4 // 4
     if u8:
-        if out is None:
-            out = torch.empty((N, H, W, 3), device=a.device, dtype=torch.uint8)
-        _chk_u8(out, "out", (N, H, W, 3))
+        out = _out(out, (N, H, W, 3), a.device, torch.uint8, 3)
         f32, q8 = None, out.data_ptr()
     else:
-        if out is None:
-            out = torch.empty((N, 3, H, W), device=a.device, dtype=torch.float32)
-        _chk(out, "out", (N, 3, H, W))
+        out = _out(out, (N, 3, H, W), a.device)
         f32, q8 = out.data_ptr(), None
-    hip_lib.check(lib.larva_dihedral_mean(a.data_ptr(), b.data_ptr(), f32, q8, N, H, W, _stream()), "larva_dihedral_mean")
+    _launch("larva_dihedral_mean", a.data_ptr(), b.data_ptr(), f32, q8, N, H, W)
     return out
 
 
@@ -1180,7 +1085,6 @@ def u8_metrics(out_u8_hwc, truth_u8_hwc, shave, channel, ssim=True, result=None)
     cropped top-left), both without `shave` border pixels, on the colour planes (channel "rgb") or the BT.601 luma plane
     ("y").  Returns the device result record (int64 [8], include/larva_hip.h; `result` to write into a given one);
     metrics_from_record turns its host copy into numbers.  Nothing comes back to the host here."""
-    lib = hip_lib.load()
     if channel not in METRIC_CHANNELS:
         raise ValueError("larvanet_amd: channel must be 'y' or 'rgb', got %r" % (channel,))
     po = _chk_u8_image(out_u8_hwc, "out")
@@ -1189,7 +1093,7 @@ def u8_metrics(out_u8_hwc, truth_u8_hwc, shave, channel, ssim=True, result=None)
         raise RuntimeError("larvanet_amd: out and truth are on different devices")
     y0, x0, h, w = metric_window(out_u8_hwc.shape, truth_u8_hwc.shape, shave, ssim)
     mode = METRIC_CHANNELS[channel]
-    nbytes = int(lib.larva_u8_metrics_workspace_bytes(h, w, mode))
+    nbytes = int(hip_lib.load().larva_u8_metrics_workspace_bytes(h, w, mode))
     if nbytes < 0:
         raise ValueError("larvanet_amd: no metric kernel for a %d x %d window" % (h, w))
     workspace = torch.empty(nbytes // 8, device=out_u8_hwc.device, dtype=torch.int64)
@@ -1199,9 +1103,8 @@ def u8_metrics(out_u8_hwc, truth_u8_hwc, shave, channel, ssim=True, result=None)
           or not result.is_contiguous() or result.device != out_u8_hwc.device):
         raise RuntimeError("larvanet_amd: result must be a contiguous int64 [%d] tensor on the images' device"
                            % METRIC_RESULT_WORDS)
-    hip_lib.check(lib.larva_u8_metrics(po, 3 * int(out_u8_hwc.shape[1]), pt, 3 * int(truth_u8_hwc.shape[1]), y0, x0, h, w,
-                                       mode, int(bool(ssim)), workspace.data_ptr(), result.data_ptr(), _stream()),
-                  "larva_u8_metrics")
+    _launch("larva_u8_metrics", po, 3 * int(out_u8_hwc.shape[1]), pt, 3 * int(truth_u8_hwc.shape[1]), y0, x0, h, w,
+            mode, int(bool(ssim)), workspace.data_ptr(), result.data_ptr())
     return result
 
 
@@ -1233,7 +1136,6 @@ def bicubic_down_u8(x_u8_hwc, scale, out=None):
     (image_utils.bicubic_downscale_u8, byte for byte), scale 2, 3 or 4, in one launch.  x may be a window into a larger
     image: pixels contiguous (strides (pitch, 3, 1) with pitch >= 3 W), any pitch and offset.  `out`: a contiguous uint8
     [h][w][3] tensor to fill."""
-    lib = hip_lib.load()
     x = x_u8_hwc
     if not isinstance(x, torch.Tensor):
         raise TypeError("larvanet_amd: x must be a uint8 tensor, got %s" % type(x).__name__)
@@ -1256,8 +1158,7 @@ def bicubic_down_u8(x_u8_hwc, scale, out=None):
         if tuple(out.shape) != (h, w, 3) or out.device != x.device:
             raise RuntimeError("larvanet_amd: out must be [%d][%d][3] on the input's device, got %s"
                                % (h, w, tuple(out.shape)))
-    hip_lib.check(lib.larva_bicubic_down_u8(x.data_ptr(), H, W, pitch, int(scale), out.data_ptr(), _stream()),
-                  "larva_bicubic_down_u8")
+    _launch("larva_bicubic_down_u8", x.data_ptr(), H, W, pitch, int(scale), out.data_ptr())
     return out
 
 
@@ -1278,7 +1179,6 @@ def bicubic_down_u8_table(data, offsets, hw, scale, out, out_offsets, planar=Fal
     `out` outside the images stay as they are.  The four small tables are read back once to check every image against
     both byte tables and to cut the flat grid (a dataset is prepared once); returns `out`."""
     import numpy as np
-    lib = hip_lib.load()
     for t, name, dt in ((data, "data", torch.uint8), (offsets, "offsets", torch.int64), (hw, "hw", torch.int32),
                         (out, "out", torch.uint8), (out_offsets, "out_offsets", torch.int64)):
         if not isinstance(t, torch.Tensor) or t.dtype != dt:
@@ -1307,9 +1207,8 @@ def bicubic_down_u8_table(data, offsets, hw, scale, out, out_offsets, planar=Fal
     if prefix[n] >= 2 ** 31:
         raise ValueError("larvanet_amd: too many tiles for one launch (%d)" % prefix[n])
     tiles = torch.from_numpy(prefix.astype(np.int32)).to(data.device)
-    hip_lib.check(lib.larva_bicubic_down_u8_table(data.data_ptr(), offsets.data_ptr(), hw.data_ptr(), n, int(scale),
-                                                  int(bool(planar)), out.data_ptr(), out_offsets.data_ptr(), tiles.data_ptr(),
-                                                  int(prefix[n]), _stream()), "larva_bicubic_down_u8_table")
+    _launch("larva_bicubic_down_u8_table", data.data_ptr(), offsets.data_ptr(), hw.data_ptr(), n, int(scale),
+            int(bool(planar)), out.data_ptr(), out_offsets.data_ptr(), tiles.data_ptr(), int(prefix[n]))
     return out
 
 
@@ -1341,17 +1240,13 @@ def i420_to_rgb_f32(frames, width, height, matrix="bt601", full_range=False, out
     """uint8 [N][pitch] I420 frames of width x height (pitch >= image_utils.i420_frame_bytes) -> float32 [N][3][H][W] RGB
     on [0, 255] in steps of 1 / 256: image_utils.i420_to_rgb_f32 per frame, bit for bit, in one launch."""
     from .image_utils import yuv_to_rgb_table
-    lib = hip_lib.load()
     W, H = _yuv_dims(width, height)
     table = hip_lib.int_array(yuv_to_rgb_table(matrix, full_range))
     N, pitch = _chk_frames(frames, "frames", W, H)
-    if out is None:
-        out = torch.empty((N, 3, H, W), device=frames.device, dtype=torch.float32)
-    _chk(out, "out", (N, 3, H, W))
+    out = _out(out, (N, 3, H, W), frames.device)
     if out.device != frames.device:
         raise RuntimeError("larvanet_amd: frames and out must be on one device")
-    hip_lib.check(lib.larva_i420_to_rgb_f32(frames.data_ptr(), pitch, out.data_ptr(), N, H, W, table, _stream()),
-                  "larva_i420_to_rgb_f32")
+    _launch("larva_i420_to_rgb_f32", frames.data_ptr(), pitch, out.data_ptr(), N, H, W, table)
     return out
 
 
@@ -1359,7 +1254,6 @@ def rgb_u8_to_i420(x, matrix="bt601", full_range=False, out=None):
     """uint8 [N][H][W][3] RGB -> uint8 [N][frame bytes] I420 frames: image_utils.rgb_u8_to_i420 per image, bit for bit, in
     one launch.  out: uint8 [N][pitch >= frame bytes] to fill (bytes of a row beyond the frame are left alone)."""
     from .image_utils import i420_frame_bytes, rgb_to_yuv_table
-    lib = hip_lib.load()
     table = hip_lib.int_array(rgb_to_yuv_table(matrix, full_range))
     _chk_u8(x, "x")
     N, H, W = (int(v) for v in x.shape[:3])
@@ -1371,8 +1265,7 @@ def rgb_u8_to_i420(x, matrix="bt601", full_range=False, out=None):
     n_out, pitch = _chk_frames(out, "out", W, H)
     if n_out != N or out.device != x.device:
         raise RuntimeError("larvanet_amd: out must hold %d frames on x's device, got %s" % (N, tuple(out.shape)))
-    hip_lib.check(lib.larva_rgb_u8_to_i420(x.data_ptr(), out.data_ptr(), pitch, N, H, W, table, _stream()),
-                  "larva_rgb_u8_to_i420")
+    _launch("larva_rgb_u8_to_i420", x.data_ptr(), out.data_ptr(), pitch, N, H, W, table)
     return out
 
 
@@ -1405,7 +1298,6 @@ def resize_u8(x_u8_hwc, out_h, out_w, out=None):
     An axis shrinks by at most 4 (ValueError beyond); any upsampling.  `out`: a contiguous uint8 tensor of the result's
     shape to fill."""
     from .image_utils import check_resize
-    lib = hip_lib.load()
     x = x_u8_hwc
     if not isinstance(x, torch.Tensor):
         raise TypeError("larvanet_amd: x must be a uint8 tensor, got %s" % type(x).__name__)
@@ -1429,8 +1321,7 @@ def resize_u8(x_u8_hwc, out_h, out_w, out=None):
     hb, hc, kx = _resize_tables(W, w, x.device)
     vb, vc, ky = _resize_tables(H, h, x.device)
     ptr = lambda t: None if t is None else t.data_ptr()
-    hip_lib.check(lib.larva_resize_u8(x.data_ptr(), out.data_ptr(), N, H, W, h, w, ptr(hb), ptr(hc), kx, ptr(vb), ptr(vc), ky,
-                                      _stream()), "larva_resize_u8")
+    _launch("larva_resize_u8", x.data_ptr(), out.data_ptr(), N, H, W, h, w, ptr(hb), ptr(hc), kx, ptr(vb), ptr(vc), ky)
     return out
 
 
@@ -1467,19 +1358,15 @@ def rgba_u8_split_f32(x, alpha_slot, k, out=None):
     """uint8 [N][H][W][4] RGBA -> float32 [N + K][3][H][W], exact, in one launch (image_utils.rgba_split_f32): slot n = the
     colour planes of image n, slot alpha_slot[n] = its alpha three times.  alpha_slot: int32 [N] on the device
     (alpha_slot_table), K of its entries name the slots N .. N + K - 1, every other entry means opaque."""
-    lib = hip_lib.load()
     _chk_tensor(x, "x", None, torch.uint8, 4)
     N, H, W = (int(v) for v in x.shape[:3])
     if min(N, H, W) < 1:
         raise RuntimeError("larvanet_amd: x must not be empty, got %s" % (tuple(x.shape),))
     k = _chk_alpha_slot(alpha_slot, N, k, x.device)
-    if out is None:
-        out = torch.empty((N + k, 3, H, W), device=x.device, dtype=torch.float32)
-    _chk(out, "out", (N + k, 3, H, W))
+    out = _out(out, (N + k, 3, H, W), x.device)
     if out.device != x.device:
         raise RuntimeError("larvanet_amd: x and out must be on one device")
-    hip_lib.check(lib.larva_rgba_u8_split_f32(x.data_ptr(), alpha_slot.data_ptr(), out.data_ptr(), N, k, H, W, _stream()),
-                  "larva_rgba_u8_split_f32")
+    _launch("larva_rgba_u8_split_f32", x.data_ptr(), alpha_slot.data_ptr(), out.data_ptr(), N, k, H, W)
     return out
 
 
@@ -1487,18 +1374,14 @@ def rgb_u8_merge_rgba(rgb, alpha_slot, n, out=None):
     """uint8 [N + K][h][w][3] (the forward's result for rgba_u8_split_f32's slots) -> uint8 [N][h][w][4] in one launch
     (image_utils.rgba_merge_u8): colour from slot n, alpha = (r + g + b + 1) // 3 of slot alpha_slot[n], 255 for an image
     without a slot.  out: a contiguous uint8 [N][h][w][4] tensor to fill."""
-    lib = hip_lib.load()
     _chk_u8(rgb, "rgb")
     n = int(n)
     M, h, w = (int(v) for v in rgb.shape[:3])
     if n < 1 or min(h, w) < 1 or not n <= M <= 2 * n:
         raise RuntimeError("larvanet_amd: rgb must hold N + K slots (N = %d, 0 <= K <= N), got %s" % (n, tuple(rgb.shape)))
     k = _chk_alpha_slot(alpha_slot, n, M - n, rgb.device)
-    if out is None:
-        out = torch.empty((n, h, w, 4), device=rgb.device, dtype=torch.uint8)
-    _chk_tensor(out, "out", (n, h, w, 4), torch.uint8, 4)
+    out = _out(out, (n, h, w, 4), rgb.device, torch.uint8, 4)
     if out.device != rgb.device:
         raise RuntimeError("larvanet_amd: rgb and out must be on one device")
-    hip_lib.check(lib.larva_rgb_u8_merge_rgba(rgb.data_ptr(), alpha_slot.data_ptr(), out.data_ptr(), n, k, h, w, _stream()),
-                  "larva_rgb_u8_merge_rgba")
+    _launch("larva_rgb_u8_merge_rgba", rgb.data_ptr(), alpha_slot.data_ptr(), out.data_ptr(), n, k, h, w)
     return out

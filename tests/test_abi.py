@@ -1,32 +1,106 @@
 """The C-ABI library loads on a machine without a GPU and exports exactly what include/larva_hip.h
 declares (no compute calls here)."""
+import ctypes
 import os
 import re
+import sys
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _declared():
-    text = open(os.path.join(ROOT, "include", "larva_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+HEADERS = {"product": os.path.join(ROOT, "include", "larva_hip.h"), "diag": os.path.join(ROOT, "tools", "larva_diag.h")}
+# every entry point a feature's tests name: the first kernels and each later feature's additions
+MUST = ("larva_conv3x3_fwd", "larva_conv3x3_wgrad", "larva_pack_weights", "larva_bicubic4_fwd",
+        "larva_l1_fwd", "larva_l1_bwd", "larva_pixel_unshuffle4", "larva_adamw_step",
+        "larva_upsample_fwd", "larva_pixel_shuffle_base", "larva_pixel_unshuffle", "larva_l1_bwd_unshuffle",
+        "larva_shuffle_l1_partial_grad",
+        "larva_f16_packed_weight_halves", "larva_f16_pack_weights", "larva_f16_head", "larva_f16_conv3x3",
+        "larva_f16_conv3x3_shuffle_base",
+        "larva_u8_hwc_to_f32_chw", "larva_f32_chw_to_u8_hwc", "larva_f16_conv3x3_shuffle_base_u8",
+        "larva_u8_metrics", "larva_u8_metrics_workspace_bytes",
+        "larva_dihedral_inputs_u8", "larva_dihedral_inputs_f32", "larva_dihedral_mean",
+        "larva_f16_conv3x3_jobs", "larva_f16_conv3x3_shuffle_base_jobs",
+        "larva_i420_to_rgb_f32", "larva_rgb_u8_to_i420", "larva_resize_u8",
+        "larva_rgba_u8_split_f32", "larva_rgb_u8_merge_rgba")
+P, I, F, D, LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_longlong
+
+
+def _declared(path=HEADERS["product"]):
+    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
     return sorted(set(re.findall(r"\b(larva_[a-z0-9_]+)\s*\(", text)))
 
 
-def test_header_declares_the_expected_entry_points():
-    names = _declared()
-    for must in ("larva_conv3x3_fwd", "larva_conv3x3_wgrad", "larva_pack_weights", "larva_bicubic4_fwd",
-                 "larva_l1_fwd", "larva_l1_bwd", "larva_pixel_unshuffle4", "larva_adamw_step"):
-        assert must in names
-
-
-def test_library_exports_every_declared_symbol():
+def _library():
     from larvanet_amd import hip_lib
     if not os.path.exists(hip_lib.LIB_PATH):
         from larvanet_amd.build import build_extension
         build_extension(verbose=False)
-    lib = hip_lib.load()
+    return hip_lib.load()
+
+
+def test_header_declares_the_expected_entry_points():
+    names = _declared()
+    for must in MUST:
+        assert must in names
+
+
+def test_entry_points_are_declared_bound_and_exported():
+    from larvanet_amd import hip_lib
+    declared, lib = _declared(), _library()
+    for name in MUST:
+        assert name in declared and name in hip_lib.SIGNATURES and hasattr(lib, name), name
+    assert lib.larva_abi_version() == 5
+
+
+@pytest.mark.parametrize("which", sorted(HEADERS))
+def test_every_declared_name_has_a_signature(which):
+    from larvanet_amd import hip_lib
+    table = hip_lib.parse_header(HEADERS[which])
+    assert sorted(table) == _declared(HEADERS[which]) and len(table) == {"product": 73, "diag": 10}[which]
+    if which == "product":
+        assert table == hip_lib.SIGNATURES
+    else:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        try:
+            import diag_lib
+        finally:
+            sys.path.pop(0)
+        assert table == diag_lib.SIGNATURES
+
+
+def test_types_are_read_from_the_header():
+    from larvanet_amd.hip_lib import SIGNATURES
+    assert SIGNATURES["larva_packed_weight_floats"][0] is LL and SIGNATURES["larva_wgrad_partial_floats"][0] is LL
+    assert SIGNATURES["larva_error_string"] == (ctypes.c_char_p, [I])
+    assert SIGNATURES["larva_abi_version"] == (I, [])
+    assert SIGNATURES["larva_adamw_step_host_copy"] == (I, [P] * 4 + [I] + [D] * 5 + [F, LL] + [P] * 3)
+    # const unsigned char* out, long long out_pitch, const unsigned char* truth, long long truth_pitch, six ints, ...
+    assert SIGNATURES["larva_u8_metrics"] == (I, [P, LL, P, LL] + [I] * 6 + [P] * 3)
+    # ..., int n, float divisor, float* out, float* host_cell, unsigned* dev_seq, void* stream
+    assert SIGNATURES["larva_loss_from_partials_to_host_seq"] == (I, [P, P, P, I, F, P, P, P, P])
+    assert SIGNATURES["larva_strip_tile_table"] == (I, [I, I, I, P, I])
+
+
+@pytest.mark.parametrize("text, named", [("int larva_x(size_t n);", "size_t n"), ("status_t larva_x(int n);", "status_t"),
+                                         ("int larva_x(void* p, n);", "larva_x"), ("int larva_x(int n) { return n; }", "larva_x"),
+                                         ("int larva_x(int n);\nint larva_x(float n);", "larva_x"), ("struct s { int a; };", "int a")])
+def test_parser_refuses_what_it_cannot_type(tmp_path, text, named):
+    from larvanet_amd import hip_lib
+    path = tmp_path / "bad.h"
+    path.write_text("/* int larva_in_a_comment(size_t n); */\n#include <stddef.h>\nint larva_ok(const float* const* p, unsigned u); // fine\n" + text)
+    with pytest.raises(RuntimeError, match=re.escape(named)):
+        hip_lib.parse_header(str(path))
+    path.write_text("void larva_ok(double d, long long n);\ntypedef struct t { int a; float* b[8]; } t;\n")
+    assert hip_lib.parse_header(str(path)) == {"larva_ok": (None, [D, LL])}
+    with pytest.raises(RuntimeError, match="nope.h is missing"):
+        hip_lib.parse_header(str(tmp_path / "nope.h"))
+
+
+def test_library_exports_every_declared_symbol():
+    from larvanet_amd import hip_lib
+    lib = _library()
     declared = _declared()
     assert sorted(hip_lib.SIGNATURES) == declared  # binding table and header agree
     for name in declared:

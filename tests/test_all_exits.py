@@ -18,9 +18,7 @@ import torch
 
 import exact_ref as X
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 gpu = pytest.mark.gpu
-NEW_ENTRY_POINTS = ("larva_f16_conv3x3_jobs", "larva_f16_conv3x3_shuffle_base_jobs")
 NEW_METHODS = ("upscale_exits", "upscale_exits_tensor", "upscale_exits_u8", "upscale_exits_u8_tensor",
                "evaluate_exits_u8_tensor")
 BLOCKS = (1, 2, 1, 1)
@@ -63,19 +61,6 @@ def _dev(a, dev):
 
 
 # ---------------------------------------------------------------- host
-def test_job_entry_points_are_declared_bound_and_exported():
-    from larvanet_amd import hip_lib
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "larva_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(larva_[a-z0-9_]+)\s*\(", text))
-    if not os.path.exists(hip_lib.LIB_PATH):
-        from larvanet_amd.build import build_extension
-        build_extension(verbose=False)
-    lib = hip_lib.load()
-    for name in NEW_ENTRY_POINTS:
-        assert name in declared and name in hip_lib.SIGNATURES and hasattr(lib, name), name
-    assert lib.larva_abi_version() == 5
-
-
 def test_all_exits_flag_parses_in_both_drivers_and_defaults_to_off():
     from larvanet_amd import evaluate, upscale_images
     for mod in (evaluate, upscale_images):

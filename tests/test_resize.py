@@ -3,7 +3,6 @@ Image.resize(..., BICUBIC) byte for byte) and kernels.resize_u8 (csrc/larva_resi
 bit for bit.  Host logic runs anywhere; the kernel tests are marked gpu and every comparison is np.array_equal."""
 import math
 import os
-import re
 
 import numpy as np
 import pytest
@@ -11,8 +10,6 @@ import torch
 
 from larvanet_amd import image_utils as U
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_ENTRY_POINTS = ("larva_resize_u8",)
 # (H, W, h, w): both axes down, nearly unchanged, exactly x4 down, one axis unchanged (each), x4 up, mixed, tiny
 PAIRS = [(48, 64, 27, 40), (37, 127, 36, 100), (64, 64, 16, 16), (40, 52, 40, 30), (33, 17, 50, 17), (20, 24, 80, 96),
          (135, 203, 72, 128), (7, 5, 2, 3)]
@@ -94,19 +91,14 @@ def test_resize_refusals():
         U.resize_u8(np.zeros((0, 5, 3), np.uint8), 8, 8)
 
 
-def test_new_entry_points_are_declared_bound_and_exported():
+def test_resize_source_is_built_and_its_entry_point_refuses_bad_arguments():
     from larvanet_amd import hip_lib
     from larvanet_amd.build import SOURCES
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "larva_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(larva_[a-z0-9_]+)\s*\(", text))
     assert "larva_resize.hip" in SOURCES
     if not os.path.exists(hip_lib.LIB_PATH):
         from larvanet_amd.build import build_extension
         build_extension(verbose=False)
     lib = hip_lib.load()
-    for name in NEW_ENTRY_POINTS:
-        assert name in declared and name in hip_lib.SIGNATURES and hasattr(lib, name), name
-    assert lib.larva_abi_version() == 5
     # refused before any launch, so this runs without a device: NULL pointers, a ratio above 4, a table's ksize that is
     # not the one of its axis (a non-NULL pointer that is never read)
     table = (hip_lib.ctypes.c_int * 4)()

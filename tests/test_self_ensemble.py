@@ -10,15 +10,11 @@ in float32 in this order (and image_to_uint8 of it), f being the plain upscale o
 with the same weights and the flag off.  The one inexact comparison is the equivariance of E, whose two sides add the same
 eight images in different orders: its bound is derived at the test."""
 import importlib
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_ENTRY_POINTS = ("larva_dihedral_inputs_u8", "larva_dihedral_inputs_f32", "larva_dihedral_mean")
 PLUGINS = ("LarvaNet", "LarvaNetV2", "LarvaLeg", "LarvaLegV2")
 BLOCKS = (1, 1)
 
@@ -103,12 +99,8 @@ def test_self_ensemble_flag_parses_and_is_off_by_default(name):
     assert args.self_ensemble is True and rest == [] and m._self_ensemble() is True
 
 
-def test_new_entry_points_are_declared_and_bound():
-    from larvanet_amd import hip_lib, build, kernels as K
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "larva_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(larva_[a-z0-9_]+)\s*\(", text))
-    for name in NEW_ENTRY_POINTS:
-        assert name in declared and name in hip_lib.SIGNATURES, name
+def test_ensemble_source_is_built_and_wrapped_and_the_drivers_document_the_flag():
+    from larvanet_amd import build, kernels as K
     assert "larva_ensemble.hip" in build.SOURCES
     assert callable(K.dihedral_inputs) and callable(K.dihedral_mean)
     for mod in ("upscale_images", "evaluate"):

@@ -13,15 +13,11 @@ and 4 - 13 % above 255.5 for every case below that has a network or a bicubic ba
 bilinear base with a network, bicubic --leg=0; x2 / x3 / x4; 64 x 64, 37 x 127, 339 x 510), so both clamps act; the tests
 assert a share of at least 1 % each on the float output as a condition on the input."""
 import importlib
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_ENTRY_POINTS = ("larva_u8_hwc_to_f32_chw", "larva_f32_chw_to_u8_hwc", "larva_f16_conv3x3_shuffle_base_u8")
 PLUGINS = ("LarvaNet", "LarvaNetV2", "LarvaLeg", "LarvaLegV2")
 BLOCKS = (4, 4, 4, 4)
 
@@ -45,19 +41,6 @@ def _blocks_image(seed, h, w):
 
 
 # ---------------------------------------------------------------- host
-def test_new_entry_points_are_declared_bound_and_exported():
-    from larvanet_amd import hip_lib
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "larva_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(larva_[a-z0-9_]+)\s*\(", text))
-    if not os.path.exists(hip_lib.LIB_PATH):
-        from larvanet_amd.build import build_extension
-        build_extension(verbose=False)
-    lib = hip_lib.load()
-    for name in NEW_ENTRY_POINTS:
-        assert name in declared and name in hip_lib.SIGNATURES and hasattr(lib, name), name
-    assert lib.larva_abi_version() == 5
-
-
 @pytest.mark.parametrize("name", PLUGINS)
 def test_plugins_have_the_u8_entry_points_and_check_arguments_before_device_work(name):
     """On a machine without a GPU nothing below may reach a kernel: every bad argument is refused on the host."""

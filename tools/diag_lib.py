@@ -11,20 +11,7 @@ if ROOT not in sys.path:
 from larvanet_amd import hip_lib   # noqa: E402
 
 DIAG_PATH = os.environ.get("LARVA_DIAG_LIB") or os.path.join(ROOT, "tools", "_diag", "diag.so")
-_p, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_float)
-_pp = ctypes.POINTER(ctypes.c_void_p)
-SIGNATURES = {
-    "larva_conv3x3_fwd_timed": (_i, [_pp, _i, _i] + [_p] * 7 + [_i] * 6 + [_p, _i, _f, _f]),
-    "larva_conv3x3_fwd_strips_timed": (_i, [_pp, _i, _i] + [_p] * 7 + [_i] * 7 + [_p, ctypes.POINTER(ctypes.c_uint), _i, _i, _p, _i, _f, _f]),
-    "larva_stamp_clock": (_i, [_p, _p]),
-    "larva_delay_ticks": (_i, [_i, _p]),
-    "larva_clock_probe": (_i, [_i, _p, _p]),
-    "larva_conv3x3_pair_chain_probe": (_i, [_p] * 4 + [_i] * 4 + [_p] * 4 + [_i, _p, _p, _p] + [_i] * 5 + [_p]),
-    "larva_conv3x3_pipeline_workspace_bytes": (ctypes.c_longlong, [_i, _i, _i]),
-    "larva_conv3x3_pipeline_plan_bytes": (ctypes.c_longlong, []),
-    "larva_conv3x3_pipeline_plan": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
-    "larva_conv3x3_pipeline_run": (_i, [_p, _i, _p]),
-}
+SIGNATURES = hip_lib.parse_header(os.path.join(ROOT, "tools", "larva_diag.h"))   # name -> (restype, argtypes)
 _lib = None
 
 
