@@ -564,6 +564,65 @@ __device__ __forceinline__ void decode_tile(const ConvArgs& a, int vb, int& n, i
   y0 = ty * G::ROWS;
 }
 
+// RoleTraits: the compile-time facts of one MFMA wave's role (run_role, below), each with the measurement that set it.
+template <int COUT, typename G, bool VEC, int EPI, int NCT, int PG0, int NPG, bool PERSIST>
+struct RoleTraits {
+  using C = ConvCfg<COUT, G>;
+  static_assert(!VEC || C::LOADER, "the 16-byte path runs with a loader wave (2 * PIECES <= 63 for every instantiated shape)");
+  static_assert(!PERSIST || VEC, "persistent tiles: the loader-wave path");
+  // Orientation of the accumulators.  Channel-major (the MFMA's A operand = weights): lane (lr, lq)
+  // holds output channels 4 lq .. 4 lq + 3 of pixel lr of its group -- what the pixel-shuffle store wants
+  // (4 sub-pixels of one HR row = 16 contiguous bytes).  Pixel-major (A = activations; every other epilogue of the
+  // 16-byte path): lane (lr, lq) holds pixels 4 lq .. 4 lq + 3 of output channel lr -- 16 contiguous bytes of an NCHW
+  // row, so the ordinary epilogues store (and fetch their mask / residual operands) with ONE 16-byte
+  // access per (channel group, pixel group) instead of four 4-byte ones: in the batched launch the
+  // store phase was 1.3 us of a conv's 12.7 us (un-instrumented ablation, tools/bench_conv_batch.py).
+  static constexpr bool kShuffleEpi = (EPI == kEpiShuffle || EPI == kEpiShuffleBase || EPI == kEpiShuffleL1);
+  static constexpr bool kPixMajor = VEC && !kShuffleEpi;
+  // The epilogue's other operands (ReLU mask, residuals, bicubic base, truth) are fetched BEFORE the K loop so that
+  // they land under it instead of being waited for after it (the mask / residual variants ran 1-1.3 us longer).
+  static constexpr int NAUX = (EPI == kEpiMask || EPI == kEpiRes1 || EPI == kEpiShuffleBase)
+                                  ? 1 : ((EPI == kEpiRes2 || EPI == kEpiShuffleL1) ? 2 : 0);
+  // PERSIST: a tile's operands are requested under its K loop, wave w's in front of chunk w (part = kEarlyAll; see the
+  // loop) -- but only the first kEarlyPairs (operand, unit) pairs q = op * NU + u (28 registers); the rest (part =
+  // kLatePart) at the head of the epilogue, into the registers the MFMA operands have just left.  Round 5: a 5-wave workgroup puts waves 0 and 4 on the same SIMD, two
+  // workgroups per CU are FOUR waves on that SIMD = at most 128 VGPRs, and the two-residual kernel held 147 (64
+  // channels: 141 with one residual, 190 with two): the second workgroup of every CU entered only when the first had
+  // left (in-kernel stamps, profiles/r05_infer_wide_layer_stamps.txt: 256 of 512 workgroups enter 28-46 us late).  Capped
+  // by the compiler instead (launch bounds) it spills 32 registers and the layer takes 78 against 70 us.
+  static constexpr int NU = NCT * NPG;
+  // (48 channels only: at 32 every variant is below 128 anyway, at 64 one workgroup per CU already keeps the matrix pipe
+  // as busy as two -- residual layers 110-113 us against 107 for conv + ReLU -- and late operands would stand exposed)
+  static constexpr int kEarlyPairs = PERSIST && COUT == 48 ? (NAUX * NU < 7 ? NAUX * NU : 7) : NAUX * NU;
+  static constexpr int kLatePart = 4, kEarlyAll = 5;
+  // Round 4: on the loader-wave path the mask / residual operands are requested BEHIND chunk 1's pieces, not in front of
+  // chunk 0's.  vmcnt retires in order: requested first (rounds 1-3), the first counted wait of the ring -- "chunk 0 has
+  // landed" -- also waited for them, and in a training step they are COLD (the ReLU mask is an activation the forward
+  // pass wrote a millisecond ago, the residuals come from two layers back): the K loop of every mask / residual link
+  // started ~1.3 us later than a conv + ReLU link's (in-kernel stamps of the captured step, profiles/r04_step_timeline_
+  // stamped.txt: workgroup life 10.4-11.5 against 9.0-10.0 us at the same 5.8-5.9 us of K loop).  Requested last, every
+  // wait of the ring leaves exactly these kAuxLoads vector loads in flight (one 16-byte load per operand and (channel
+  // group, pixel group) unit with pixel-major accumulators) and the vmcnt(0) behind the K loop collects them.
+  // kAuxLoads must not EXCEED the loads the compiler really emits between chunk 1's pieces and the first wait (a
+  // smaller real count would let a wait pass with a piece still in flight): tools/check_aux_loads.py counts them in
+  // the ISA of every instantiation, and larvanet_amd/build.py runs it on every build.
+  // (not for the pixel-shuffle exits: their base / truth operands are 2 x 7 sixteen-byte loads per wave from the HR
+  // images, and requested late the batched L1 launch got SLOWER -- 66 against 58 us under rocprofv3, the exits' forward
+  // 120 against 112 us in the stamped step: they then queue in front of the loader wave's chunk-2 pieces)
+  static constexpr bool kAuxLate = VEC && !kShuffleEpi && !(LARVA_DIAG & 6) && NAUX > 0 && !PERSIST;
+  static constexpr int kAuxLoads = kAuxLate ? NAUX * NCT * NPG : 0;
+};
+
+// One element of a mode-0 epilogue: o = acc + bias, then ReLU / mask / the residual adds, in the reference's order.
+template <int EPI, typename Aux>
+__device__ __forceinline__ float fuse_element(float o, const Aux& aux, int c, int p, int r) {
+  if constexpr (EPI == kEpiRelu) o = o < 0.f ? 0.f : o;   // torch.relu: NaN stays NaN (fmaxf would return 0)
+  if constexpr (EPI == kEpiMask) o = (aux[0][c][p][r] <= 0.f) ? 0.f : o;   // threshold_backward: a NaN mask passes
+  if constexpr (EPI == kEpiRes1 || EPI == kEpiRes2) o += aux[0][c][p][r];
+  if constexpr (EPI == kEpiRes2) o += aux[1][c][p][r];
+  return o;
+}
+
 // One MFMA wave's share of a tile: cout groups [ct0, ct0 + NCT) x pixel groups [PG0, PG0 + NPG).
 // PERSIST (conv3x3_mfma_persist_kernel): the workgroup walks tiles blockIdx.x, + gridDim.x, ... of the launch; the loader
 // wave streams EVERY chunk (run_loader_persist), the ring runs on across the tiles, and this wave only meets the loader
@@ -571,8 +630,9 @@ __device__ __forceinline__ void decode_tile(const ConvArgs& a, int vb, int& n, i
 template <int COUT, typename G, bool VEC, int EPI, int NCT, int PG0, int NPG, bool PERSIST = false>
 __device__ __forceinline__ void run_role(const ConvArgs& a, float* smem, int ct0, int wave, int n, int y0, int x0, int tid) {
   using C = ConvCfg<COUT, G>;
-  static_assert(!VEC || C::LOADER, "the 16-byte path runs with a loader wave (2 * PIECES <= 63 for every instantiated shape)");
-  static_assert(!PERSIST || VEC, "persistent tiles: the loader-wave path");
+  using T = RoleTraits<COUT, G, VEC, EPI, NCT, PG0, NPG, PERSIST>;
+  constexpr bool kShuffleEpi = T::kShuffleEpi, kPixMajor = T::kPixMajor;
+  constexpr int NAUX = T::NAUX;
   const int lane = tid & 63;
   const int lr = lane & 15, lq = lane >> 4;
   float* const out_ptr = a.out;
@@ -584,15 +644,6 @@ __device__ __forceinline__ void run_role(const ConvArgs& a, float* smem, int ct0
   struct { int H, W, pitch, plain; } k = {a.H, a.W, a.pitch, a.plain_stores};
   asm volatile("" : "+s"(k.H), "+s"(k.W), "+s"(k.pitch), "+s"(k.plain));
 
-  // Orientation of the accumulators.  Channel-major (the MFMA's A operand = weights): lane (lr, lq)
-  // holds output channels 4 lq .. 4 lq + 3 of pixel lr of its group -- what the pixel-shuffle store wants
-  // (4 sub-pixels of one HR row = 16 contiguous bytes).  Pixel-major (A = activations; every other epilogue of the
-  // 16-byte path): lane (lr, lq) holds pixels 4 lq .. 4 lq + 3 of output channel lr -- 16 contiguous bytes of an NCHW
-  // row, so the ordinary epilogues store (and fetch their mask / residual operands) with ONE 16-byte
-  // access per (channel group, pixel group) instead of four 4-byte ones: in the batched launch the
-  // store phase was 1.3 us of a conv's 12.7 us (un-instrumented ablation, tools/bench_conv_batch.py).
-  constexpr bool kShuffleEpi = (EPI == kEpiShuffle || EPI == kEpiShuffleBase || EPI == kEpiShuffleL1);
-  constexpr bool kPixMajor = VEC && !kShuffleEpi;
   f32x4 bias[NCT];
 #pragma unroll
   for (int c = 0; c < NCT; ++c) bias[c] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -605,23 +656,7 @@ __device__ __forceinline__ void run_role(const ConvArgs& a, float* smem, int ct0
     }
   };
 
-  // The epilogue's other operands (ReLU mask, residuals, bicubic base, truth) are fetched BEFORE the K loop so that
-  // they land under it instead of being waited for after it (the mask / residual variants ran 1-1.3 us longer).
-  constexpr int NAUX = (EPI == kEpiMask || EPI == kEpiRes1 || EPI == kEpiShuffleBase)
-                           ? 1 : ((EPI == kEpiRes2 || EPI == kEpiShuffleL1) ? 2 : 0);
   f32x4 aux[NAUX > 0 ? NAUX : 1][NAUX > 0 ? NCT : 1][NAUX > 0 ? NPG : 1];
-  // PERSIST: a tile's operands are requested under its K loop, wave w's in front of chunk w (part = kEarlyAll; see the
-  // loop) -- but only the first kEarlyPairs (operand, unit) pairs q = op * NU + u (28 registers); the rest (part =
-  // kLatePart) at the head of the epilogue, into the registers the MFMA operands have just left.  Round 5: a 5-wave workgroup puts waves 0 and 4 on the same SIMD, two
-  // workgroups per CU are FOUR waves on that SIMD = at most 128 VGPRs, and the two-residual kernel held 147 (64
-  // channels: 141 with one residual, 190 with two): the second workgroup of every CU entered only when the first had
-  // left (in-kernel stamps, profiles/r05_infer_wide_layer_stamps.txt: 256 of 512 workgroups enter 28-46 us late).  Capped
-  // by the compiler instead (launch bounds) it spills 32 registers and the layer takes 78 against 70 us.
-  constexpr int NU = NCT * NPG;
-  // (48 channels only: at 32 every variant is below 128 anyway, at 64 one workgroup per CU already keeps the matrix pipe
-  // as busy as two -- residual layers 110-113 us against 107 for conv + ReLU -- and late operands would stand exposed)
-  constexpr int kEarlyPairs = PERSIST && COUT == 48 ? (NAUX * NU < 7 ? NAUX * NU : 7) : NAUX * NU;
-  constexpr int kLatePart = 4, kEarlyAll = 5;
   // (tried: `part` as a compile-time tag behind a switch, so that the units of the unrolled nest lose their scalar
   // branches -- the four copies of the loads cost registers instead: 71 / 80 us per residual layer against 63 / 66)
   auto load_aux = [&](int part = -1) {
@@ -633,8 +668,8 @@ __device__ __forceinline__ void run_role(const ConvArgs& a, float* smem, int ct0
         const int y = min(y0 + prow, a.H - 1), x = min(x0 + pcol * 16 + lr, a.W - 1);
         // does this call request operand `op` of unit (c, p)?   (wave-uniform, constant after unrolling)
         auto want = [&](int op) {
-          const int q = op * NU + c * NPG + p;
-          return part < 0 ? true : part == kLatePart ? q >= kEarlyPairs : q < kEarlyPairs;
+          const int q = op * T::NU + c * NPG + p;
+          return part < 0 ? true : part == T::kLatePart ? q >= T::kEarlyPairs : q < T::kEarlyPairs;
         };
         if constexpr (kShuffleEpi) {
           const int HH = 4 * a.H, WW = 4 * a.W;
@@ -697,25 +732,9 @@ __device__ __forceinline__ void run_role(const ConvArgs& a, float* smem, int ct0
         }
       }
   };
-  // Round 4: on the loader-wave path the mask / residual operands are requested BEHIND chunk 1's pieces, not in front of
-  // chunk 0's.  vmcnt retires in order: requested first (rounds 1-3), the first counted wait of the ring -- "chunk 0 has
-  // landed" -- also waited for them, and in a training step they are COLD (the ReLU mask is an activation the forward
-  // pass wrote a millisecond ago, the residuals come from two layers back): the K loop of every mask / residual link
-  // started ~1.3 us later than a conv + ReLU link's (in-kernel stamps of the captured step, profiles/r04_step_timeline_
-  // stamped.txt: workgroup life 10.4-11.5 against 9.0-10.0 us at the same 5.8-5.9 us of K loop).  Requested last, every
-  // wait of the ring leaves exactly these kAuxLoads vector loads in flight (one 16-byte load per operand and (channel
-  // group, pixel group) unit with pixel-major accumulators) and the vmcnt(0) behind the K loop collects them.
-  // kAuxLoads must not EXCEED the loads the compiler really emits between chunk 1's pieces and the first wait (a
-  // smaller real count would let a wait pass with a piece still in flight): tools/check_aux_loads.py counts them in
-  // the ISA of every instantiation, and larvanet_amd/build.py runs it on every build.
-  // (not for the pixel-shuffle exits: their base / truth operands are 2 x 7 sixteen-byte loads per wave from the HR
-  // images, and requested late the batched L1 launch got SLOWER -- 66 against 58 us under rocprofv3, the exits' forward
-  // 120 against 112 us in the stamped step: they then queue in front of the loader wave's chunk-2 pieces)
-  constexpr bool kAuxLate = VEC && !kShuffleEpi && !(LARVA_DIAG & 6) && NAUX > 0 && !PERSIST;
-  constexpr int kAuxLoads = kAuxLate ? NAUX * NCT * NPG : 0;
   auto load_early = [&]() {
     load_bias();
-    if constexpr (NAUX > 0 && !kAuxLate && !(LARVA_DIAG & 4)) load_aux();
+    if constexpr (NAUX > 0 && !T::kAuxLate && !(LARVA_DIAG & 4)) load_aux();
   };
   int pstage = 0;   // PERSIST: the ring's stage, running on across the workgroup's tiles
   for (int vb = blockIdx.x;; vb += gridDim.x) {   // (one trip unless PERSIST)
@@ -746,7 +765,7 @@ __device__ __forceinline__ void run_role(const ConvArgs& a, float* smem, int ct0
         // the loader wave's next chunks: +14 us per layer with two residual operands), and a wave pays one uniform branch
         // per chunk.  (Until late in round 5: a quarter of EVERY wave's units per chunk -- a scalar branch per unit in
         // front of four chunks' first MFMAs: 62.8 against 61.2 us for a one-residual layer, same box.)
-        if (chunk == my_chunk) load_aux(kEarlyAll);
+        if (chunk == my_chunk) load_aux(T::kEarlyAll);
         __builtin_amdgcn_sched_barrier(0);
       }
       mfma_chunk<COUT, G, NCT, PG0, NPG, kPixMajor>(smem + pstage * C::STAGE_FLOATS, ct0, lane, acc);
@@ -754,8 +773,8 @@ __device__ __forceinline__ void run_role(const ConvArgs& a, float* smem, int ct0
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (kEarlyPairs < NAUX * NU) {
-      load_aux(kLatePart);
+    if constexpr (T::kEarlyPairs < NAUX * T::NU) {
+      load_aux(T::kLatePart);
       __builtin_amdgcn_sched_barrier(0);
     }
   } else if constexpr (VEC) {
@@ -786,7 +805,7 @@ __device__ __forceinline__ void run_role(const ConvArgs& a, float* smem, int ct0
       const ChunkSrc cs1 = chunk_src<COUT, G>(a, min(1, last), n);
 #pragma unroll
       for (int i = 0; i < C::NPW; ++i) dma_piece<COUT, G>(pl, i, wave, cs1, st1);
-      if constexpr (kAuxLate) {   // the youngest vector loads of the wave (see above)
+      if constexpr (T::kAuxLate) {   // the youngest vector loads of the wave (see above)
         __builtin_amdgcn_sched_barrier(0);
         load_aux();
         __builtin_amdgcn_sched_barrier(0);
@@ -799,8 +818,8 @@ __device__ __forceinline__ void run_role(const ConvArgs& a, float* smem, int ct0
       // stage that chunk + 2 is about to overwrite.
       if constexpr ((LARVA_DIAG & 256) != 0) {
         // timing ablation (with bit 1: nothing is staged): no barrier between the chunks
-      } else if (chunk == 0) wait_and_barrier<((LARVA_DIAG & 2) ? 0 : C::NPW) + kAuxLoads, ((LARVA_DIAG & 2) ? 0 : C::NPW), kAuxLoads>();
-      else wait_and_barrier<kAuxLoads, 0, kAuxLoads>();
+      } else if (chunk == 0) wait_and_barrier<((LARVA_DIAG & 2) ? 0 : C::NPW) + T::kAuxLoads, ((LARVA_DIAG & 2) ? 0 : C::NPW), T::kAuxLoads>();
+      else wait_and_barrier<T::kAuxLoads, 0, T::kAuxLoads>();
       if (chunk == 0) stamp(2);
       stamp(8 + (chunk < 7 ? chunk : 7));
       if constexpr (!(LARVA_DIAG & 1)) mfma_chunk<COUT, G, NCT, PG0, NPG, kPixMajor>(smem + stage * C::STAGE_FLOATS, ct0, lane, acc);
@@ -916,11 +935,7 @@ __device__ __forceinline__ void run_role(const ConvArgs& a, float* smem, int ct0
           if (kInterior || (y < k.H && xb < k.pitch)) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              float o = v[r];
-              if constexpr (EPI == kEpiRelu) o = o < 0.f ? 0.f : o;   // torch.relu: NaN stays NaN (fmaxf would return 0)
-              if constexpr (EPI == kEpiMask) o = (aux[0][c][p][r] <= 0.f) ? 0.f : o;   // threshold_backward: a NaN mask passes
-              if constexpr (EPI == kEpiRes1 || EPI == kEpiRes2) o += aux[0][c][p][r];
-              if constexpr (EPI == kEpiRes2) o += aux[1][c][p][r];
+              const float o = fuse_element<EPI>(v[r], aux, c, p, r);
               v[r] = (kInterior || xb + r < k.W) ? o : 0.f;   // columns [W, pitch) are kept at zero for the next layer
             }
             if constexpr (kPlain) *reinterpret_cast<f32x4*>(out_ptr + idx) = v;
@@ -964,11 +979,7 @@ __device__ __forceinline__ void run_role(const ConvArgs& a, float* smem, int ct0
           const bool real = x < k.W;  // columns [W, pitch) are kept at zero for the next layer
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            float o = v[r];
-            if constexpr (EPI == kEpiRelu) o = o < 0.f ? 0.f : o;   // torch.relu: NaN stays NaN (fmaxf would return 0)
-            if constexpr (EPI == kEpiMask) o = (aux[0][c][p][r] <= 0.f) ? 0.f : o;   // threshold_backward: a NaN mask passes
-            if constexpr (EPI == kEpiRes1 || EPI == kEpiRes2) o += aux[0][c][p][r];
-            if constexpr (EPI == kEpiRes2) o += aux[1][c][p][r];
+            float o = fuse_element<EPI>(v[r], aux, c, p, r);
             o = real ? o : 0.f;
             if constexpr ((LARVA_DIAG & 16) != 0) out_ptr[idx0 + r * plane] = o;
             else __builtin_nontemporal_store(o, &out_ptr[idx0 + r * plane]);
@@ -995,33 +1006,59 @@ __device__ __forceinline__ void fetch_args(const ConvArgs& a) {
                "s"(a.tab16[0]), "s"(a.tab16[16]));
 }
 
+// One workgroup on one tile, with THE role table: wave 4 (16-byte path) streams, the CT cout groups x ROWS * PC pixel
+// groups of units are dealt to waves 0..3 (one per SIMD) as evenly as a rectangular (cout groups) x (pixel groups)
+// ownership allows.  !GIVEN (whole-tensor kernels): also the kernel's head -- arguments, tile blockIdx.x, wave index and
+// priority; GIVEN (the strip kernel, which looks its tile up itself): wave, tile and thread index come from the caller.
 // VEC: 2 workgroups per CU (launch bound 2 waves/SIMD caps the registers at 256).
-template <int COUT, bool VEC, int EPI, typename G = GeoWide>
-__device__ __forceinline__ void conv_tile(const ConvArgs& a, float* smem) {
-  if constexpr ((LARVA_DIAG & 8) != 0) return;
-  stamp(0);
-  fetch_args(a);
-  const int tile = xcd_remap(blockIdx.x, a.nwg);
-  const int t2 = div_by_magic(tile, a.magic_tx);
-  const int tx = tile - t2 * a.tiles_x;
-  const int n = div_by_magic(t2, a.magic_ty);
-  const int ty = t2 - n * a.tiles_y;
-  const int x0 = tx * G::COLS, y0 = ty * G::ROWS;
-  const int tid = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // Convs form the dependent chain of a step; weight-gradient workgroups that share the CU run
-  // at priority 0 and take the matrix pipe only when these waves cannot use it.
-  __builtin_amdgcn_s_setprio(1);
-
+template <int COUT, bool VEC, int EPI, typename G = GeoWide, bool GIVEN = false>
+__device__ __forceinline__ void conv_tile(const ConvArgs& a, float* smem, int wave = 0, int n = 0, int y0 = 0, int x0 = 0, int tid = 0) {
+  static_assert(COUT == 48 || COUT == 32 || COUT == 64, "unsupported channel count");
+  if constexpr (!GIVEN) {
+    if constexpr ((LARVA_DIAG & 8) != 0) return;
+    stamp(0);
+    fetch_args(a);
+    // (spelled out, not decode_tile: through its reference parameters five 48-channel kernels come out differently)
+    const int tile = xcd_remap(blockIdx.x, a.nwg);
+    const int t2 = div_by_magic(tile, a.magic_tx);
+    const int tx = tile - t2 * a.tiles_x;
+    n = div_by_magic(t2, a.magic_ty);
+    const int ty = t2 - n * a.tiles_y;
+    x0 = tx * G::COLS, y0 = ty * G::ROWS;
+    tid = threadIdx.x;
+    wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // Convs form the dependent chain of a step; weight-gradient workgroups that share the CU run
+    // at priority 0 and take the matrix pipe only when these waves cannot use it.
+    __builtin_amdgcn_s_setprio(1);
+  }
   if constexpr (VEC) {
     if (wave == 4) {
-      if constexpr (!(LARVA_DIAG & 2)) run_loader<COUT, G>(a, smem, tid & 63, n, y0, x0);
+      if constexpr (GIVEN || !(LARVA_DIAG & 2)) run_loader<COUT, G>(a, smem, tid & 63, n, y0, x0);
       return;
     }
   }
-  // ROWS * 3 pixel groups x CT cout groups, dealt to the 4 waves (one per SIMD) as evenly as a
-  // rectangular (cout groups) x (pixel groups) ownership allows.
-  if constexpr (G::ROWS == 4) {
+  if constexpr (G::COLS == 16) {
+    // Strip tiles (5 x 16 / 4 x 16): ROWS pixel groups
+    static_assert(VEC && ConvCfg<COUT, G>::LOADER, "the strip kernel is launched with a loader wave");
+    if constexpr (COUT == 64) {
+      // x 4 cout groups = 20 / 16 units: every wave one cout group x all pixel groups (5,5,5,5 / 4,4,4,4)
+      run_role<COUT, G, VEC, EPI, 1, 0, G::ROWS>(a, smem, wave, wave, n, y0, x0, tid);
+    } else if constexpr (COUT == 48) {
+      // x 3 cout groups: waves 0..2 own one cout group x the first ROWS-1 pixel groups, wave 3
+      // all three cout groups of the last pixel group (15 units -> 4,4,4,3; 12 -> 3,3,3,3)
+      if (wave < 3) run_role<COUT, G, VEC, EPI, 1, 0, G::ROWS - 1>(a, smem, wave, wave, n, y0, x0, tid);
+      else run_role<COUT, G, VEC, EPI, 3, G::ROWS - 1, 1>(a, smem, 0, wave, n, y0, x0, tid);
+    } else if constexpr (G::ROWS == 5) {
+      // 32 channels, 5 pixel groups x 2 cout groups = 10 units -> 3,3,2,2
+      if (wave < 2) run_role<COUT, G, VEC, EPI, 1, 0, 3>(a, smem, wave, wave, n, y0, x0, tid);
+      else if (wave == 2) run_role<COUT, G, VEC, EPI, 2, 3, 1>(a, smem, 0, wave, n, y0, x0, tid);
+      else run_role<COUT, G, VEC, EPI, 2, 4, 1>(a, smem, 0, wave, n, y0, x0, tid);
+    } else {
+      // 32 channels, 4 pixel groups x 2 cout groups = 8 units -> 2,2,2,2
+      if (wave < 2) run_role<COUT, G, VEC, EPI, 1, 0, 2>(a, smem, wave, wave, n, y0, x0, tid);
+      else run_role<COUT, G, VEC, EPI, 1, 2, 2>(a, smem, wave - 2, wave, n, y0, x0, tid);
+    }
+  } else if constexpr (G::ROWS == 4) {
     static_assert(VEC && (COUT == 48 || COUT == 32), "4 x 48 tiles: the 16-byte path at 48 / 32 channels");
     if constexpr (COUT == 48) {  // 36 -> 9,9,9,9
       if (wave < 3) run_role<COUT, G, VEC, EPI, 1, 0, 9>(a, smem, wave, wave, n, y0, x0, tid);
@@ -1030,14 +1067,13 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, float* smem) {
       if (wave < 2) run_role<COUT, G, VEC, EPI, 1, 0, 6>(a, smem, wave, wave, n, y0, x0, tid);
       else run_role<COUT, G, VEC, EPI, 1, 6, 6>(a, smem, wave - 2, wave, n, y0, x0, tid);
     }
-  } else if constexpr (COUT == 48) {  // 27 -> 7,7,7,6
+  } else if constexpr (COUT == 48) {  // 3 x 48: 27 -> 7,7,7,6
     if (wave < 3) run_role<COUT, G, VEC, EPI, 1, 0, 7>(a, smem, wave, wave, n, y0, x0, tid);
     else run_role<COUT, G, VEC, EPI, 3, 7, 2>(a, smem, 0, wave, n, y0, x0, tid);
   } else if constexpr (COUT == 32) {  // 18 -> 5,5,4,4
     if (wave < 2) run_role<COUT, G, VEC, EPI, 1, 0, 5>(a, smem, wave, wave, n, y0, x0, tid);
     else run_role<COUT, G, VEC, EPI, 1, 5, 4>(a, smem, wave - 2, wave, n, y0, x0, tid);
-  } else {  // COUT == 64: 36 -> 9,9,9,9
-    static_assert(COUT == 64, "unsupported channel count");
+  } else {  // 64: 36 -> 9,9,9,9
     run_role<COUT, G, VEC, EPI, 1, 0, 9>(a, smem, wave, wave, n, y0, x0, tid);
   }
 }
@@ -1128,7 +1164,9 @@ __global__ __launch_bounds__((ConvCfg<COUT>::THREADS_DMA), kWgPerCu) void conv3x
     run_loader_persist<COUT, G>(a, smem, tid & 63);
     return;
   }
-  if constexpr (COUT == 48) {   // 27 units -> 7,7,7,6 (as conv_tile)
+  // (the 3 x 48 rows of conv_tile's role table, repeated: with this body one call further down four of these kernels
+  // come out with other instructions)
+  if constexpr (COUT == 48) {   // 27 units -> 7,7,7,6
     if (wave < 3) run_role<COUT, G, true, EPI, 1, 0, 7, true>(a, smem, wave, wave, 0, 0, 0, tid);
     else run_role<COUT, G, true, EPI, 3, 7, 2, true>(a, smem, 0, wave, 0, 0, 0, tid);
   } else if constexpr (COUT == 32) {   // 18 -> 5,5,4,4
@@ -1140,38 +1178,8 @@ __global__ __launch_bounds__((ConvCfg<COUT>::THREADS_DMA), kWgPerCu) void conv3x
   }
 }
 
-// Strip tiles (48 output channels, LDS-DMA path): every workgroup looks its tile up in a table of
-// ONE image's tiles -- 5 x 16 or 4 x 16 pixels -- and runs the matching instantiation.  ROWS pixel
-// groups x 3 cout groups: waves 0..2 own one cout group x the first ROWS-1 pixel groups, wave 3 all
-// three cout groups of the last pixel group (15 units -> 4,4,4,3; 12 -> 3,3,3,3).
-template <int COUT, int EPI, typename G>
-__device__ __forceinline__ void strip_roles(const ConvArgs& a, float* smem, int wave, int n, int y0, int x0, int tid) {
-  static_assert(ConvCfg<COUT, G>::LOADER, "the strip kernel is launched with a loader wave");
-  static_assert(COUT == 48 || COUT == 32 || COUT == 64, "strip tiles: 32, 48 or 64 output channels");
-  if (wave == 4) {
-    run_loader<COUT, G>(a, smem, tid & 63, n, y0, x0);
-    return;
-  }
-  if constexpr (COUT == 64) {
-    // ROWS pixel groups x 4 cout groups = 20 / 16 units: every wave one cout group x all pixel groups (5,5,5,5 / 4,4,4,4)
-    run_role<COUT, G, true, EPI, 1, 0, G::ROWS>(a, smem, wave, wave, n, y0, x0, tid);
-  } else if constexpr (COUT == 48) {
-    // ROWS pixel groups x 3 cout groups: waves 0..2 own one cout group x the first ROWS-1 pixel groups, wave 3
-    // all three cout groups of the last pixel group (15 units -> 4,4,4,3; 12 -> 3,3,3,3)
-    if (wave < 3) run_role<COUT, G, true, EPI, 1, 0, G::ROWS - 1>(a, smem, wave, wave, n, y0, x0, tid);
-    else run_role<COUT, G, true, EPI, 3, G::ROWS - 1, 1>(a, smem, 0, wave, n, y0, x0, tid);
-  } else if constexpr (G::ROWS == 5) {
-    // 32 channels, 5 pixel groups x 2 cout groups = 10 units -> 3,3,2,2
-    if (wave < 2) run_role<COUT, G, true, EPI, 1, 0, 3>(a, smem, wave, wave, n, y0, x0, tid);
-    else if (wave == 2) run_role<COUT, G, true, EPI, 2, 3, 1>(a, smem, 0, wave, n, y0, x0, tid);
-    else run_role<COUT, G, true, EPI, 2, 4, 1>(a, smem, 0, wave, n, y0, x0, tid);
-  } else {
-    // 32 channels, 4 pixel groups x 2 cout groups = 8 units -> 2,2,2,2
-    if (wave < 2) run_role<COUT, G, true, EPI, 1, 0, 2>(a, smem, wave, wave, n, y0, x0, tid);
-    else run_role<COUT, G, true, EPI, 1, 2, 2>(a, smem, wave - 2, wave, n, y0, x0, tid);
-  }
-}
-
+// Strip tiles (LDS-DMA path): every workgroup looks its tile up in a table of ONE image's tiles -- 5 x 16 or
+// 4 x 16 pixels -- and runs the matching instantiation of conv_tile.
 template <int COUT, int EPI>
 __global__ __launch_bounds__(320, kWgPerCu) void conv3x3_mfma_strip_kernel(ConvArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1194,8 +1202,8 @@ __global__ __launch_bounds__(320, kWgPerCu) void conv3x3_mfma_strip_kernel(ConvA
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   __builtin_amdgcn_s_setprio(1);
-  if (e >> 31) strip_roles<COUT, EPI, GeoS5>(a, smem, wave, n, y0, x0, tid);
-  else strip_roles<COUT, EPI, GeoS4>(a, smem, wave, n, y0, x0, tid);
+  if (e >> 31) conv_tile<COUT, true, EPI, GeoS5, true>(a, smem, wave, n, y0, x0, tid);
+  else conv_tile<COUT, true, EPI, GeoS4, true>(a, smem, wave, n, y0, x0, tid);
 }
 template <int COUT>
 constexpr size_t kStripLdsBytes = ConvCfg<COUT, GeoS5>::LDS_BYTES_DMA > ConvCfg<COUT, GeoS4>::LDS_BYTES_DMA ? ConvCfg<COUT, GeoS5>::LDS_BYTES_DMA
