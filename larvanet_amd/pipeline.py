@@ -12,7 +12,9 @@ Every buffer a copy touches belongs to the pipeline: `depth` slots of flat pinne
 largest image seen and viewed at each image's size.  The forward's result is copied (device to device, ~10 us for an
 8 MB image) into the slot's own output buffer on the compute stream, because a replayed graph's output buffer is
 overwritten by the next image of that shape and an eager result is the caching allocator's, which knows nothing of
-the copy stream.  A slot is reused only after its device-to-host copy has been waited for, which orders every reuse.
+the copy stream.  A slot is reused only after its device-to-host copy has been waited for, which orders every reuse; a
+device buffer that is new (first use, or grown) is the compute stream's allocation, so the copy stream waits for that stream
+once before it first writes there (tests/test_stream_order.py).
 
 evaluate_stream() is the same pipeline over (input, truth) pairs: the truth image travels in on the copy stream beside
 the input, the metric launch (kernels.u8_metrics) follows the forward on the compute stream, and only the 64-byte result
@@ -67,6 +69,9 @@ class _Slot:
             return torch.empty(n, dtype=torch.uint8, pin_memory=True)
         buf = torch.empty(n, dtype=torch.uint8, device=self.device)
         buf.record_stream(self.copy_stream)
+        # The block comes from the current (compute) stream's pool: it may be an activation a forward still in flight there
+        # has just released, and the copy stream is the first to write an input buffer.  Once per growth.
+        self.copy_stream.wait_stream(torch.cuda.current_stream())
         return buf
 
     def views(self, which, shape, host=True):
