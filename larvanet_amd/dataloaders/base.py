@@ -7,6 +7,20 @@ def create_loader():
     return BaseLoader()
 
 
+class SeededStream:
+    """sampler_state() / load_sampler_state() of a loader whose every draw comes from ONE RandomState, `self.rng`, seeded
+    from --data_seed: the state is that generator's.  Without a seed the stream is fresh entropy per process and there
+    is nothing to continue: None."""
+
+    def sampler_state(self):
+        if getattr(self.args, "data_seed", None) is None:
+            return None
+        return self.rng.get_state()
+
+    def load_sampler_state(self, state):
+        self.rng.set_state(state)
+
+
 class BaseLoader:
     def __init__(self):
         self.is_threaded = False
@@ -40,6 +54,16 @@ class BaseLoader:
         --lr_from_hr makes the LR images itself)."""
         _, hr, name = self.get_image_pair(image_index, scale)
         return hr, name
+
+    # a training state (models/LarvaNet.save_training_state) continues the patch stream through these two
+    def sampler_state(self):
+        """The sampler's position in its random stream as a picklable object, or None when this loader cannot be
+        continued (threads that prefetch, a stream that was never seeded)."""
+        return None
+
+    def load_sampler_state(self, state):
+        """Continue the stream from a sampler_state() of a loader prepared with the same flags."""
+        raise NotImplementedError("%s cannot continue a patch stream" % type(self).__name__)
 
     # threaded loaders only
     def start_training_queue_runner(self, batch_size, input_patch_size):

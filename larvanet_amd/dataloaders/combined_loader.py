@@ -31,6 +31,13 @@ class CombinedLoader(DIV2KLoader):
         super().prepare(scales)
         self._queues = {s: queue.Queue(maxsize=self.args.data_queue_size) for s in scales}
 
+    def sampler_state(self):
+        """None: the producer threads draw from generators of their own and run ahead of the step by a queue of batches."""
+        return None
+
+    def load_sampler_state(self, state):
+        raise NotImplementedError("combined_loader prefetches on threads: its patch stream cannot be continued")
+
     def _image(self, key, path):
         with self._cache_lock:
             return super()._image(key, path)

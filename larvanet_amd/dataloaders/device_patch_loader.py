@@ -29,7 +29,7 @@ import torch
 
 from .. import dist as ldist
 from .. import kernels as K
-from .base import BaseLoader
+from .base import BaseLoader, SeededStream
 
 
 def create_loader():
@@ -151,11 +151,12 @@ def make_lr_tables(tables, device):
     return tables
 
 
-class DevicePatchLoader(BaseLoader):
+class DevicePatchLoader(SeededStream, BaseLoader):
     is_device = True
 
     def parse_args(self, args):
-        parser = argparse.ArgumentParser()
+        # no prefix matching: the model's --lr travels through this parser and is a prefix of --lr_from_hr
+        parser = argparse.ArgumentParser(allow_abbrev=False)
         parser.add_argument("--device_source", type=str, default="div2k_train_loader",
                             help="loader plugin that supplies the images to make resident")
         parser.add_argument("--data_seed", type=int, default=None)

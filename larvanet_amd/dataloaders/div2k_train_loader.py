@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from .. import dist as ldist
-from .base import BaseLoader
+from .base import BaseLoader, SeededStream
 
 
 def create_loader():
@@ -42,7 +42,7 @@ def augment_pair(rng, input_image, truth_image, scale, input_patch_size):
     return lr, hr
 
 
-class DIV2KLoader(BaseLoader):
+class DIV2KLoader(SeededStream, BaseLoader):
     float_images = True
 
     def _add_args(self, parser):

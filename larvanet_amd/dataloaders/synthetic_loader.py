@@ -6,7 +6,7 @@ import copy
 import numpy as np
 
 from .. import dist as ldist
-from .base import BaseLoader
+from .base import BaseLoader, SeededStream
 from .div2k_train_loader import augment_pair
 
 
@@ -28,7 +28,7 @@ def make_pair(index, lr_h, lr_w, scale, as_float):
     return lr.astype(np.uint8), hr.astype(np.uint8)
 
 
-class SyntheticLoader(BaseLoader):
+class SyntheticLoader(SeededStream, BaseLoader):
     def parse_args(self, args):
         parser = argparse.ArgumentParser()
         parser.add_argument("--synthetic_images", type=int, default=8)

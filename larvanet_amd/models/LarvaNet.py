@@ -61,6 +61,19 @@ def create_model():
     return LarvaNet()
 
 
+def atomic_save(obj, path):
+    """torch.save under a temporary name in the same directory, then os.replace: a save that is interrupted leaves the
+    file that had this name before as it was, and nothing partial under a final name."""
+    head, tail = os.path.split(path)
+    tmp = os.path.join(head, ".%s.tmp%d" % (tail, os.getpid()))
+    try:
+        torch.save(obj, tmp)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+
+
 def init_conv(conv, scale=0.1):
     """Reference init (models/LarvaNet.py:22-31): kaiming normal (fan_in, a=0) * scale, zero bias."""
     nn.init.kaiming_normal_(conv.weight, a=0, mode="fan_in")
@@ -389,6 +402,9 @@ class LarvaNet(InferenceMixin, BaseModel):
         # group's slice of the bucket can be all-reduced beside the second) on ONE GPU, without collectives
         self.force_split_backward = os.environ.get("LARVA_FORCE_SPLIT", "0") != "0"
         self.args = None
+        # the driver's training loader (train_larva.main sets it): save_training_state() stores its sampler_state() and
+        # restore_training_state() hands it back, so that a resumed run continues the patch stream
+        self.train_loader = None
         self.precision = "fp32"       # (prepare() takes it from --precision)
         self.grad_bucket = None
         self.time_allreduce = False   # bench.py: time every exposed all-reduce, as a pair of events in ...
@@ -879,7 +895,7 @@ class LarvaNet(InferenceMixin, BaseModel):
     def save(self, base_path):
         """Bare state_dict with the reference's key names (models/LarvaNet.py:183-185)."""
         save_path = os.path.join(base_path, "model_step%d_vol%.0fG.pth" % (self.global_step, self.total_volume / 1e9))
-        torch.save({k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()}, save_path)
+        atomic_save({k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()}, save_path)
         return save_path
 
     def restore(self, ckpt_path, target=None):
@@ -887,18 +903,25 @@ class LarvaNet(InferenceMixin, BaseModel):
         self.model.invalidate_packed_weights()
 
     def save_training_state(self, base_path):
-        """Optimizer moments, LR-scheduler state, step / volume counters and RNG states next to
+        """Optimizer moments, LR-scheduler state, step / volume counters, RNG states and the training loader's place in
+        its patch stream ("train_loader": `train_loader.sampler_state()`, None when there is none to continue) next to
         the reference-compatible weight file (the reference can only resume weights + --global_step,
-        models/LarvaNet.py:183-188, train_larva.py:43-47,81-83)."""
+        models/LarvaNet.py:183-188, train_larva.py:43-47,81-83).  Data parallel: rank 0 writes the file and the other
+        ranks' streams are not in it, so no stream is stored."""
         path = os.path.join(base_path, "train_state_step%d.pth" % self.global_step)
         opt = self.optim.training_state() if hasattr(self.optim, "training_state") else \
             {"flat": False, "torch": self.optim.state_dict()}
-        torch.save({"global_step": self.global_step, "total_volume": self.total_volume,
-                    "temp_volume": self.temp_volume, "optimizer": opt, "scheduler": self.scheduler.state_dict(),
-                    "torch_rng": torch.get_rng_state(), "numpy_rng": np.random.get_state()}, path)
+        sampler = None
+        if self.train_loader is not None and ldist.world_size() == 1:
+            sampler = self.train_loader.sampler_state()
+        atomic_save({"global_step": self.global_step, "total_volume": self.total_volume,
+                     "temp_volume": self.temp_volume, "optimizer": opt, "scheduler": self.scheduler.state_dict(),
+                     "torch_rng": torch.get_rng_state(), "numpy_rng": np.random.get_state(),
+                     "train_loader": sampler}, path)
         return path
 
     def restore_training_state(self, path):
+        """-> True when the training loader's patch stream was continued too; otherwise one warning line says why not."""
         st = torch.load(path, map_location="cpu", weights_only=False)
         self.global_step, self.total_volume, self.temp_volume = st["global_step"], st["total_volume"], st["temp_volume"]
         if hasattr(self.optim, "load_training_state"):
@@ -908,6 +931,23 @@ class LarvaNet(InferenceMixin, BaseModel):
         self.scheduler.load_state_dict(st["scheduler"])
         torch.set_rng_state(st["torch_rng"])
         np.random.set_state(st["numpy_rng"])
+        why = None
+        if "train_loader" not in st:
+            why = "the file was written before training states held one"
+        elif ldist.world_size() > 1:
+            why = "data parallel: a training state holds no per-rank streams"
+        elif st["train_loader"] is None:
+            why = "the saving run's loader had none (a threaded loader, or no --data_seed)"
+        elif self.train_loader is None:
+            why = "no training loader is attached to the plugin"
+        elif self.train_loader.sampler_state() is None:
+            why = "this run's loader cannot continue one (a threaded loader, or no --data_seed)"
+        if why is not None:
+            if ldist.is_main():
+                print("WARNING: %s holds no sampler state to continue: %s. The patch stream restarts." % (os.path.basename(path), why))
+            return False
+        self.train_loader.load_sampler_state(st["train_loader"])
+        return True
 
     def get_model(self):
         return self.model

@@ -80,6 +80,31 @@ class FlatAdamW(torch.optim.AdamW):
             self._v.copy_(st["v"].to(self._v.device))
             for g, saved in zip(self.param_groups, st["param_groups"]):
                 g.update(saved)
+        elif not st.get("flat") and self._flat_p is not None:
+            # a per-tensor state (a run that had left the flat path, or plain torch.optim.AdamW) into a flat optimizer:
+            # torch numbers the parameters in param_groups order, which is _plist's
+            saved, off = st["torch"], 0
+            steps = set()
+            for i, p in enumerate(self._plist):
+                n = p.numel()
+                s = saved["state"].get(i)
+                if s is None:   # (a parameter that never took a step)
+                    self._m[off:off + n].zero_()
+                    self._v[off:off + n].zero_()
+                else:
+                    if tuple(s["exp_avg"].shape) != tuple(p.shape):
+                        raise RuntimeError("larvanet_amd: optimizer state %d has shape %s, the parameter %s"
+                                           % (i, tuple(s["exp_avg"].shape), tuple(p.shape)))
+                    self._m[off:off + n].copy_(s["exp_avg"].reshape(-1).to(self._m.device))
+                    self._v[off:off + n].copy_(s["exp_avg_sq"].reshape(-1).to(self._v.device))
+                    steps.add(int(float(s["step"])))
+                off += n
+            if len(steps) > 1:   # (the flat launch has one bias correction for all parameters)
+                raise RuntimeError("larvanet_amd: per-tensor optimizer state with different step counts %s cannot be "
+                                   "loaded into the flat optimizer" % sorted(steps))
+            self._t = steps.pop() if steps else 0
+            for g, sg in zip(self.param_groups, saved["param_groups"]):
+                g.update({k: v for k, v in sg.items() if k != "params"})
         elif not st.get("flat"):
             super().load_state_dict(st["torch"])
         else:

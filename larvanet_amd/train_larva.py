@@ -118,9 +118,20 @@ def main(argv=None, v2=False):
     if args.restore_path is not None:
         model.restore(ckpt_path=args.restore_path, target=args.restore_target)
         print("restored the model")
+    # the plugin stores the loader's place in its patch stream with every training state and hands it back on resume
+    model.train_loader = loader
     if args.resume_state is not None:
-        model.restore_training_state(args.resume_state)
+        model.restore_training_state(args.resume_state)   # (warns, in one line, when the patch stream is not continued)
         print("restored the training state at step %d" % model.global_step)
+    elif args.save_train_state and rank == 0:
+        why = None
+        if world > 1:
+            why = "data parallel: only rank 0's file is written"
+        elif loader.sampler_state() is None:
+            why = "%s has no sampler state (a threaded loader, or no --data_seed)" % args.dataloader
+        if why is not None:
+            print("WARNING: the training states of this run will not continue the patch stream: %s. "
+                  "A run resumed from one restarts the patch stream." % why)
 
     writers = {s: (make_summary_writer(os.path.join(args.train_path, "x%d" % s)) if rank == 0 else _NullSummary())
                for s in scales}
