@@ -30,6 +30,7 @@ class EarlyExitFlags:
     """The plugin side of `--leg`: the flag itself and the halo of the shortened route."""
 
     has_cooldown = False   # (V2's flag set)
+    tail_on_inference_route = False   # (LarvaLegV2: the V2 tail is trained, never on the --leg route)
 
     def _add_args(self, parser):
         # flag set and defaults of models/LarvaLeg.py:46-61 and models/LarvaLegV2.py:46-61 (= LarvaNetV2's plus --leg)

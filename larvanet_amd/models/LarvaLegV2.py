@@ -16,4 +16,6 @@ class LarvaNetModule(EarlyExitRoute, V2.LarvaNetModule):
 
 
 class LarvaNet(EarlyExitFlags, V2.LarvaNet):
+    # EarlyExitFlags comes first in the bases: its tail_on_inference_route = False is the one V2.LarvaNet.prepare() reads
+    # here, so more than 8 bodies are refused for training only (the --leg route never reaches the tail's merge conv)
     module_class = LarvaNetModule

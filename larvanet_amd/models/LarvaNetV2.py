@@ -69,6 +69,20 @@ class LarvaNet(V1.LarvaNet):
 
     module_class = LarvaNetModule
     has_cooldown = False
+    # the tail's merge conv reads every body's output as one source tensor each; the conv kernels (kernels.conv3x3,
+    # kernels.f16_conv3x3) take at most this many
+    MAX_MERGED_BODIES = 8
+    tail_on_inference_route = True   # (False for --leg plugins: their route ends at a body's exit)
+
+    def prepare(self, is_training, scales, global_step=0):
+        n = int(self.args.num_modules)
+        if n > self.MAX_MERGED_BODIES and (is_training or self.tail_on_inference_route):
+            name = type(self).__module__.rsplit(".", 1)[-1]
+            raise ValueError("larvanet_amd: %s merges the outputs of at most %d bodies in its tail (one source tensor of "
+                             "the merge conv each), got --num_modules=%d%s"
+                             % (name, self.MAX_MERGED_BODIES, n, "" if self.tail_on_inference_route else
+                                "; inference stops at --leg and prepares, training runs the tail"))
+        return super().prepare(is_training, scales, global_step)
 
     def _add_args(self, parser):
         # V2's flag set and defaults (models/LarvaNetV2.py:46-60): no --lr_step / --cooldown

@@ -564,6 +564,26 @@ def test_every_refusal_keeps_its_type_and_its_text():
     assert not wrong, "\n".join("%s:\n  got  %s: %s\n  want %s: %s" % (l, g[0], g[1], w[0], w[1]) for l, g, w in wrong)
 
 
+def test_v2_with_more_bodies_than_the_merge_conv_takes_is_refused_at_prepare():
+    """LarvaNetV2 --num_modules=9: the tail's merge conv would have nine source tensors and the conv kernels take eight.
+    Refused by prepare(), for training and inference alike, not by a RuntimeError inside the first forward."""
+    import importlib
+    nine = ["--num_modules=9", "--num_blocks=1,1,1,1,1,1,1,1,1"]
+    text = P_ + ("%s merges the outputs of at most 8 bodies in its tail (one source tensor of the merge conv each), got "
+                 "--num_modules=9%s")
+
+    def prepare(name, training):
+        m = importlib.import_module("larvanet_amd.models." + name).create_model()
+        m.parse_args(nine)
+        return _refusal(lambda: m.prepare(is_training=training, scales=[4]))
+
+    for training in (False, True):
+        assert prepare("LarvaNetV2", training) == (V, text % ("LarvaNetV2", ""))
+    assert prepare("LarvaLegV2", True) == (V, text % ("LarvaLegV2", "; inference stops at --leg and prepares, training runs the tail"))
+    assert prepare("LarvaLegV2", False)[0] is None   # (--leg=4 of nine: the tail is never on the route)
+    assert prepare("LarvaNet", False)[0] is None     # (nine exits, no merge conv)
+
+
 def test_passing_images_and_frames_are_not_refused():
     from larvanet_amd import pipeline as P
     rgb, rgba = np.zeros((H, W, 3), np.uint8), np.zeros((H, W, 4), np.uint8)
